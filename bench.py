@@ -3,6 +3,18 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 16]
                     [--scaling strong|weak] [--global-blocks G] [--blocks-per-gpu B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+timed launches' own kernel split): nothing else touches the GPU.
+`--dump-outputs DIR` also writes what the last timed step left in the output
+buffers (DIR/cost.npy, DIR/tour.npy, blocks of all ranks in instance order).
+`--full` adds everything measured or checked beside the headline: the
+left-fold check of the timed result, the other scaling form, time to optimal,
+the i32 extension, the K2/K3 probes, the rocprofv3 counter passes and measured
+VALU peaks of the roofline, the reference's multi-block runs and the CPU
+baselines (each still switched off by its own --no-* option).
 
 One STEP = one pass of K1 (the batched Held-Karp forward kernel + its
 backtracking kernel, in launches of at most 16384 blocks) over this rank's
@@ -811,6 +823,31 @@ def pmc_child(args):
     ctx.synchronize()
 
 
+DUMP_LIMIT = 64 * 1000 * 1000  # bytes of .npy payload --dump-outputs may write
+
+
+def dump_outputs(path, group, rank, n, cost, tour):
+    """--dump-outputs DIR: the timed path's outputs after its last step, the
+    blocks of all ranks in instance order: DIR/cost.npy (blocks,) float64 and
+    DIR/tour.npy (blocks, n + 1) float32 (city indices, exact).  Above
+    DUMP_LIMIT bytes a fixed, seeded sample of blocks is written instead, with
+    their block numbers as DIR/block_index.npy (float64)."""
+    parts = group.gather((cost, tour))
+    if rank != 0:
+        return
+    cost = np.concatenate([p[0] for p in parts]).astype(np.float64)
+    tour = np.concatenate([p[1] for p in parts]).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    per_block = 8 + 4 * (n + 1) + 8
+    keep = DUMP_LIMIT // per_block
+    if cost.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(0).choice(cost.shape[0], size=keep, replace=False))
+        cost, tour = cost[idx], tour[idx]
+        np.save(os.path.join(path, "block_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "cost.npy"), cost)
+    np.save(os.path.join(path, "tour.npy"), tour)
+
+
 def plumbing(args, world, rank):
     """--plumbing (CPU, no GPU): the multi-rank orchestration alone — shard
     bounds of every rank, the barrier-bracketed region and the max over
@@ -845,6 +882,11 @@ def main():
     ap.add_argument("--blocks-per-gpu", type=int, default=16384, help="weak scaling (and the weak probe)")
     ap.add_argument("--k2-n", type=int, default=32, help="cities of the K2 strong-scaling instance")
     ap.add_argument("--k2-seed", type=int, default=35)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs to DIR/cost.npy and DIR/tour.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: result check, other scaling form, time to "
+                         "optimal, i32 extension, K2/K3 probes, counter passes, reference and CPU baselines")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--no-tto", action="store_true", help="skip the time-to-optimal probes")
@@ -868,6 +910,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.plumbing:
         return plumbing(args, world, rank)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
     group = Group(world)
 
     n = args.n
@@ -916,15 +961,21 @@ def main():
                            f"(per-step sums)"}
     ctx.k1_split_timing(False)
 
-    # correctness of what was timed: every tour is a permutation whose left fold equals its cost
-    cost = ctx.download(dc, (Bp,), np.float64)
-    tour = ctx.download(dt, (Bp, n + 1), np.int32)
-    for b in range(0, Bp, max(1, Bp // 64)):
-        assert sorted(tour[b, :n].tolist()) == list(range(n)) and tour[b, 0] == 0 and tour[b, n] == 0
-        acc = 0.0
-        for i in range(n):
-            acc = acc + d[b, tour[b, i], tour[b, i + 1]]
-        assert acc == cost[b], "timed result failed the left-fold check"
+    # what the last timed step left in the output buffers
+    cost = tour = None
+    if full or args.dump_outputs:
+        cost = ctx.download(dc, (Bp,), np.float64) if Bp else np.empty((0,), np.float64)
+        tour = ctx.download(dt, (Bp, n + 1), np.int32) if Bp else np.empty((0, n + 1), np.int32)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, group, rank, n, cost, tour)
+    # --full: correctness of what was timed: every tour is a permutation whose left fold equals its cost
+    if full:
+        for b in range(0, Bp, max(1, Bp // 64)):
+            assert sorted(tour[b, :n].tolist()) == list(range(n)) and tour[b, 0] == 0 and tour[b, n] == 0
+            acc = 0.0
+            for i in range(n):
+                acc = acc + d[b, tour[b, i], tour[b, i + 1]]
+            assert acc == cost[b], "timed result failed the left-fold check"
 
     relax = tspgpu.relaxations_per_block(n)
     total_blocks = global_blocks * args.steps
@@ -933,7 +984,7 @@ def main():
     # the other scaling form beside the headline: with strong scaling, every
     # rank also solves a fixed --blocks-per-gpu shard (weak), and vice versa
     other_scaling = None
-    if os.environ.get("BENCH_OTHER_SCALING", "1") != "0":
+    if full and os.environ.get("BENCH_OTHER_SCALING", "1") != "0":
         try:
             other_scaling = scaling_probe(ctx, args, world, rank, group, n, relax)
         except Exception as e:  # noqa: BLE001 - the probe must never cost the headline line
@@ -942,7 +993,7 @@ def main():
     # time to optimal: one block through the ABI (in process), and the whole
     # program as a child process (the reference's definition)
     tto = {}
-    if not args.no_tto:
+    if full and not args.no_tto:
         t_one = []
         one = [shard.block(0)]
         for _ in range(10):
@@ -963,7 +1014,7 @@ def main():
 
     # extension probe: the same launch on the rounded integer matrices (K1 i32)
     i32 = None
-    if os.environ.get("BENCH_I32", "1") != "0":
+    if full and os.environ.get("BENCH_I32", "1") != "0":
         try:
             di = np.rint(d).astype(np.int32)
             pi, ci, ti = ctx.upload(di), ctx.alloc(Bp * 4), ctx.alloc(Bp * (n + 1) * 4)
@@ -994,7 +1045,7 @@ def main():
             i32 = {"error": f"{type(e).__name__}: {e}"}
 
     k2 = k2s = exh = tsplib = None
-    if not args.no_k2 and os.environ.get("BENCH_K2", "1") != "0":
+    if full and not args.no_k2 and os.environ.get("BENCH_K2", "1") != "0":
         try:
             kgroup, backend = k2_group(world, local_rank)
         except Exception as e:  # noqa: BLE001
@@ -1031,9 +1082,9 @@ def main():
         return
     alg_bytes_per_block = tspgpu.table_bytes_per_block(n)
     prof = None
-    if world == 1 and not args.no_pmc:
+    if full and world == 1 and not args.no_pmc:
         prof = pmc_profile(n, min(Bp, 4096), cu, kname)
-    peaks = valu_peaks() if world == 1 else None
+    peaks = valu_peaks() if full and world == 1 else None
     if i32 and "relaxations_per_s" in i32 and (peaks or {}).get("i32 relaxation min-only (add,min)"):
         # K1 on int32 distances against the integer VALU issue rate of its own
         # min-only relaxation (v_add_u32 + v_min_i32, registers only, this GPU),
@@ -1055,17 +1106,17 @@ def main():
         except Exception as e:  # noqa: BLE001
             k2["pmc"] = {"error": f"{type(e).__name__}: {e}"}
     cpu = cpu_opt = refmb = k3 = None
-    if world == 1 and not args.no_k3:
+    if full and world == 1 and not args.no_k3:
         try:
             k3 = k3_merge()
         except Exception as e:  # noqa: BLE001
             k3 = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_ref_multiblock:
+    if full and world == 1 and not args.no_ref_multiblock:
         try:
             refmb = reference_multiblock(n)
         except Exception as e:  # noqa: BLE001
             refmb = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(n)
         try:
             cpu_opt = cpu_optimized(n)
@@ -1101,6 +1152,7 @@ def main():
         "ranks_per_gpu": -(-world // ndev),
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
         "ms_per_step": wall_max / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": args.scaling,

@@ -20,8 +20,41 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def test_plain_run_dumps_what_the_timed_path_computed(tmp_path):
+    """A plain run (no --full) times the steps and nothing else; --dump-outputs
+    writes the last step's costs and tours, which equal the CPU oracle's."""
+    import oracle_py as O
+
+    n, G = 9, 300
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--n", str(n), "--global-blocks", str(G), "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(G * tspgpu.relaxations_per_block(n) / (line["ms_per_step"] * 1e-3))
+    for key in ("other_scaling", "k2_single_instance", "k2_strong_scaling", "k1_i32_extension", "cpu_baseline",
+                "counters", "k3_merge", "reference_multiblock"):
+        assert line[key] is None, key
+    assert sorted(os.listdir(out)) == ["cost.npy", "tour.npy"]
+    cost, tour = np.load(out / "cost.npy"), np.load(out / "tour.npy")
+    assert cost.dtype == np.float64 and cost.shape == (G,)
+    assert tour.dtype == np.float32 and tour.shape == (G, n + 1)
+    sys.path.insert(0, ROOT)
+    from bench import Shard
+
+    d = Shard(n, G, 0, G).distances()
+    for b in range(0, G, 7):
+        oc, ot = O.solve_block(d[b])
+        assert cost[b] == oc and tour[b].tolist() == ot, b
+
+
 def test_bench_two_ranks_end_to_end(gpu_ctx):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--global-blocks", "1000", "--blocks-per-gpu", "512", "--no-pmc", "--no-cpu-baseline", "--no-tto",
            "--no-ref-multiblock", "--k2-n", "18", "--k2-seed", "1"]
     env = dict(os.environ, BENCH_I32="0")

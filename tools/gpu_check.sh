@@ -31,11 +31,11 @@ for s in $STEPS; do
     case $s in
     tests) run gpu_tests 600 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread ;;
     smoke) run smoke 180 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python -u bench.py ;;
+    bench) run bench 600 python -u bench.py --full ;;
     prof)
         rm -rf $OUT/prof_$TAG
         run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- \
-            python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-tto ;;
+            python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-pmc --no-tto ;;
     esac
 done
 exit 0
