@@ -141,11 +141,11 @@ int tspgpu_device_info(const tspgpu_ctx *ctx, int *cu_count, char *name, int nam
  * the last launch used and the DP relaxations per block for n cities,
  * N(N-1)2^(N-2) with N = n-1 (tsp.cpp:442-471). */
 int tspgpu_last_grid(const tspgpu_ctx *ctx);
-/* K1 variant the last batched launch used: 6 = sub-cube restructured
- * (hk_sub_kernel), 5 = sub-cube tiled (hk_tiled_kernel), 4 = ping-pong +
- * parent words, 2 = compact + prefetch, ... (heldkarp_kernel). */
+/* K1 variant the last batched launch used: 6 = sub-cube (hk_sub_kernel),
+ * 4 = ping-pong + parent words, 2 = compact layer pass + prefetch (both
+ * heldkarp_kernel); 0 for n = 2.  (1 and 5 named variants that were retired.) */
 int tspgpu_last_variant(const tspgpu_ctx *ctx);
-/* Measurement aid for variants 5 and 6, which run two kernels per chunk of at
+/* Measurement aid for variant 6, which runs two kernels per chunk of at
  * most 16384 blocks (the forward pass, then hk_tiled_backtrack): with split
  * timing enabled every chunk also records HIP events before, between and
  * after the two kernels, on the launch's stream.  tspgpu_k1_last_split_ms

@@ -191,10 +191,10 @@ def test_k1_batches_reference_goldens_default_kernel(gpu_ctx, case, variant, kno
     """The reference's own tsp() outputs for 522 blocks per n = 13..16 (tie-heavy
     lattices and uniform cities), solved in ONE batch: a batch of more than
     one block per CU runs the large-batch kernel — variant 6 (hk_sub_kernel,
-    the default: the configuration ./tsp 16 65536 times) and variant 5
-    and the layer-by-layer kernel (variant 2, knob K1=2) — both against the
-    reference itself.  (Variant 5's forward kernels ship only in K1_SWEEP
-    builds: test_k1_variants_gpu covers every configuration compiled in.)"""
+    the default: the configuration ./tsp 16 65536 times) — and the
+    layer-by-layer kernel (variant 2, knob K1=2), both against the reference
+    itself.  (test_k1_variants_gpu covers every variant-6 configuration
+    compiled in.)"""
     blocks = O.k1_batch_blocks(case)
     n = case["n"]
     ctx = gpu_ctx

@@ -2,15 +2,18 @@
 CPU oracle at the sizes where it is the default — including the variant
 switches that happen inside one call:
 
-  * n = 16, B >= 2 x CUs: the restructured sub-cube kernel (variant 6,
-    hk_sub.h) is the default; variant 5 (hk_tiled.h), variant 4 (ping-pong +
-    parent words) and variant 2 are forced through the knob K1 (read when a
-    context is created);
-  * every variant-5/6 configuration compiled in (k1_cfg.h, knob TILED_CFG),
+  * n = 16, B >= 2 x CUs: the sub-cube kernel (variant 6, hk_sub.h) is the
+    default; variant 4 (ping-pong + parent words) and variant 2 are forced
+    through the knob K1 (read when a context is created); K1=5, the retired
+    variant 5, is an alias of the fall-back for sizes without a variant-6
+    configuration (variant 4 at n = 16 f64);
+  * every variant-6 configuration compiled in (k1_cfg.h, knob TILED_CFG),
     f64 and i32;
+  * K1 = 0 and 1 (retired layer-kernel variants) run variant 2, on an LDS
+    table and on a global one;
   * tie-heavy blocks (integer lattice 0..3, 0..39) mixed with random ones;
   * one block solved alone (variant 2: fewer blocks than CUs) equals its row
-    of the large batch (variant 5).
+    of the large batch (variant 6).
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -86,10 +89,22 @@ def test_n16_large_batch_every_variant(variant):
         used = _check(ctx, d, ref)
     finally:
         ctx.close()
-    expect = 6 if variant is None else variant
-    if variant == 5 and not any(v == 5 for v, *_ in _k1_cfgs()):
-        expect = 4  # (no variant-5 forward kernel in a product build: the n = 16 fallback)
-    assert used == expect
+    # (K1=5: the retired variant 5 is an alias of the n = 16 f64 fall-back, variant 4)
+    assert used == {None: 6, 5: 4}.get(variant, variant)
+
+
+@pytest.mark.parametrize("k1", [0, 1])
+@pytest.mark.parametrize("n", [5, 13])
+def test_retired_layer_variants_run_variant_2(k1, n):
+    """K1 = 0 and 1 named layer-kernel variants that no longer exist: both now
+    run variant 2, on the LDS table (n = 5) and the global table (n = 13)."""
+    d = _blocks(n, 8, 70 + n)
+    ref = _oracle_all(("f64", n, 8, 70 + n), d)
+    ctx = _ctx(k1)
+    try:
+        assert _check(ctx, d, ref) == 2
+    finally:
+        ctx.close()
 
 
 @pytest.mark.parametrize("n,vb,expect", [(13, 8, 6), (14, 8, 6), (15, 8, 6), (16, 8, 6), (12, 8, 2), (16, 4, 6),
@@ -112,16 +127,16 @@ def test_large_batch_default_per_size(n, vb, expect):
 
 def _k1_cfgs():
     """(variant, id, value bytes, n) of every configuration compiled into the
-    library: the product rows of k1_cfg.h (sweep rows only in K1_SWEEP builds)."""
+    library: the rows of k1_cfg.h's TSPGPU_SUB_PRODUCT_CFGS (variant 6)."""
     import re
 
     path = os.path.join(os.path.dirname(tspgpu.PKG_DIR), "tsp-mpi-reduction_amd", "csrc", "k1_cfg.h")
     text = open(path).read()
-    out = []
-    for variant, macro in ((5, "TSPGPU_TILED_PRODUCT_CFGS"), (6, "TSPGPU_SUB_PRODUCT_CFGS")):
-        body = text[text.index(f"#define {macro}(X)"):].split("\n\n", 1)[0]
-        for m in re.finditer(r"X\((\d+), (\w+), (\d+), (\d+),", body):
-            out.append((variant, int(m.group(1)), 8 if m.group(2) == "double" else 4, int(m.group(3)) + 1))
+    body = text[text.index("#define TSPGPU_SUB_PRODUCT_CFGS(X)"):].split("\n\n", 1)[0]
+    out = [(6, int(m.group(1)), 8 if m.group(2) == "double" else 4, int(m.group(3)) + 1)
+           for m in re.finditer(r"X\((\d+), (\w+), (\d+), (\d+),", body)]
+    # (an empty or partial parse must not silently run fewer cases: the five product rows are there)
+    assert len(out) >= 5 and {60, 61, 62, 63, 64} <= {c[1] for c in out}, out
     return out
 
 

@@ -67,7 +67,7 @@ def emulate(d):
             for j, m in enumerate(members):
                 for k in range(N):
                     acc[k] = min(acc[k], row[j] + d[m, k + 1])
-            # descending k with suffix sums (heldkarp_impl.h scatter_row)
+            # descending k with suffix sums (the rank formula of the retired member sweep's scatter)
             q = s1 = s2 = 0
             for k in range(N - 1, -1, -1):
                 inn = T >> k & 1

@@ -19,7 +19,7 @@ import csv, glob, sys, collections, statistics
 vals = collections.defaultdict(list)
 for f in glob.glob(sys.argv[1] + "/p*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "hk_sub_kernel" in r["Kernel_Name"] or "hk_tiled_kernel" in r["Kernel_Name"]:
+        if "hk_sub_kernel" in r["Kernel_Name"]:
             vals[r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k in sorted(vals):
     print(k, statistics.median(vals[k]))

@@ -1,10 +1,10 @@
 """K1 large-batch kernels on the GPU (development aid; the parity tests proper
 are in tests/): for each requested (variant, configuration) the batch of
-`./tsp n B 1000 1000` blocks is solved, compared bit for bit with variant 5's
-default (costs and tours), and timed with HIP events on the context's stream
+`./tsp n B 1000 1000` blocks is solved, compared bit for bit with K1=5 (the
+layer kernel variant 6 falls back to: costs and tours), and timed with HIP events on the context's stream
 — the whole launch, then the forward and backtracking kernels apart.
 
-    python tools/k1_time.py n B vb spec [spec ...]     spec = variant[:cfg], e.g. 6 5 6:65
+    python tools/k1_time.py n B vb spec [spec ...]     spec = variant[:cfg], e.g. 6 5 6:60
 Prints one JSON line per spec.
 """
 import json

@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/pmc_ifetch.sh TAG KERNEL_SUBSTR'   (env: TSPGPU_K1, TSPGPU_TILED_CFG)
 set -u
 cd "$(dirname "$0")/.."
-TAG=${1:-ifetch}; KERN=${2:-hk_tiled_kernel}
+TAG=${1:-ifetch}; KERN=${2:-hk_sub_kernel}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp

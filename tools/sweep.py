@@ -19,7 +19,7 @@ from bench import Shard  # noqa: E402
 
 ns = [int(a) for a in sys.argv[1:]] or [16, 14, 12]
 # (K1 variant, threads, workgroups per CU); SWEEP="v,t,w;v,t,w" overrides
-configs = [(0, 512, 2), (1, 256, 4), (1, 256, 8), (1, 512, 2), (1, 512, 4), (1, 1024, 2)]
+configs = [(2, 256, 4), (2, 256, 8), (2, 512, 2), (2, 512, 4), (2, 1024, 1), (4, 512, 1)]
 if os.environ.get("SWEEP"):
     configs = [tuple(int(x) for x in c.split(",")) for c in os.environ["SWEEP"].split(";")]
 for n in ns:

@@ -38,15 +38,15 @@ struct LaunchArgs {
     int vbytes;             // 8: f64 distances, 4: i32 distances
     bool use_lds;
     int threads;            // 256 / 512 / 1024 threads per workgroup (global-table kernels)
-    int variant;            // layer pass: 0 = member sweep over all N cities, 1 = compact (non-members only),
-                            // 2 = compact with the next row prefetched
+    int variant;            // layer pass: 2 = compact with the next row prefetched,
+                            // 4 = 2 + ping-pong values and parent words (12..16 cities)
     hipStream_t stream;
 };
 
 void host_layer_info(int N, LayerInfo *info);
 size_t table_doubles(int N);
 hipError_t launch_heldkarp(const LaunchArgs &a, int grid);
-size_t lds_bytes_for(int N, bool lds_table, int threads, bool compact, int vbytes = 8);
+size_t lds_bytes_for(int N, bool lds_table, int threads, int vbytes = 8);
 int threads_for(int N, bool lds_table, int requested);
 
 }  // namespace tspgpu

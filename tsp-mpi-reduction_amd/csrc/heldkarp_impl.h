@@ -1,5 +1,5 @@
-// Templates of the K1 Held-Karp kernels; instantiated per N in hk_n*.hip so the
-// instantiations compile in parallel (see heldkarp.hip for the dispatch).
+// Templates of the K1 Held-Karp layer kernels; instantiated one unit per kernel
+// under k1l/ (tools/gen_hk_units.py; see heldkarp.hip for the dispatch).
 #pragma once
 // K1 — batched exact Held-Karp for gfx950 (MI355X): kernel templates.
 //
@@ -29,10 +29,12 @@
 //
 // Work split: layer t -> t+1 is one pass over the C(N,t) SOURCE rows T,
 // compiled separately for every t (offsets, counts, row length are constants).
-// A thread issues the t loads of its next row early (software pipelining into
-// VGPRs), parks the current row in a thread-private LDS slot, sweeps the
-// members m of T (d-row of m from LDS, N running minima acc[k] in VGPRs) and
-// stores acc[k] for every k not in T to G[T+k][k] (its unique writer).
+// A thread owns source rows, issues the t loads of its next row early
+// (software pipelining into VGPRs), relaxes the N-t destinations k not in T
+// over the members m of T (d-row of m from LDS) and stores each to G[T+k][k]
+// (its unique writer): layer_pass_compact below.  (The earlier member sweep
+// over all N cities, variant 0, and the compact pass without prefetch on
+// global tables, variant 1, are in git history: last in commit 8f46298.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -127,15 +129,16 @@ __host__ __device__ constexpr int lds_end_layers(int N, int threads, int vb = 8)
     while (2 * (a + 1) < N && low_bytes(N, a + 1, vb) + high_bytes(N, a + 1, vb) <= budget - base) ++a;
     return a;
 }
-// LDS: binomials | distance rows | rank LUT | table (LDS_TABLE) | end layers
-// (compact global kernels) | per-thread row slots (member-sweep global kernels)
-__host__ __device__ constexpr size_t lds_bytes(int N, bool lds_table, int threads, bool compact, int vb = 8)
+// LDS: binomials | distance rows | rank LUT | table (LDS_TABLE) or end layers
+// (global-table kernels).  The 2 KB binomial area is no longer read (only the
+// retired member sweep did); it stays because the LDS size sets the
+// LDS-table kernels' grid (tspgpu.cpp), so dropping it needs a measurement.
+__host__ __device__ constexpr size_t lds_bytes(int N, bool lds_table, int threads, int vb = 8)
 {
     return lds_base_bytes(N, vb) +
            (lds_table ? ((size_t)N << (N - 1)) * vb
-                      : (compact ? low_bytes(N, lds_end_layers(N, threads, vb), vb) +
-                                       high_bytes(N, lds_end_layers(N, threads, vb), vb)
-                                 : (size_t)(N - 1) * threads * 8));
+                      : low_bytes(N, lds_end_layers(N, threads, vb), vb) +
+                            high_bytes(N, lds_end_layers(N, threads, vb), vb));
 }
 
 // colex rank through the three-digit LUT (heldkarp.h)
@@ -147,18 +150,6 @@ __device__ __forceinline__ uint32_t lut_rank(uint32_t mask, const int *rl)
     if constexpr (N > 7) r += rl[kRankR1 + ((mask >> 7) & 127u) * 8 + __builtin_popcount(lo)];
     if constexpr (N > 14) r += rl[kRankR1 + kRankR2 + (mask >> 14) * 15 + __builtin_popcount(mask & 0x3fffu)];
     return (uint32_t)r;
-}
-
-__device__ __forceinline__ int colex_rank(uint32_t mask, const int *binom)
-{
-    int rank = 0, j = 0;
-    while (mask) {
-        const int b = __builtin_ctz(mask);
-        rank += binom[b * kBinomStride + j + 1];
-        ++j;
-        mask &= mask - 1u;
-    }
-    return rank;
 }
 
 // minimum over the wave (all 64 lanes active): DPP row reduction + readlane (wave.h)
@@ -205,33 +196,19 @@ struct GlobalTableT<double> {
         return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(idx * 8u), 0,
                                                                                TSPGPU_VAL_LOAD_AUX));
     }
-    // a store at an offset past num_records is dropped by the buffer range
-    // check: predication without a branch
-    __device__ __forceinline__ void store_if(bool pred, uint32_t idx, double v) const
-    {
-        using u2 = decltype(__builtin_amdgcn_raw_buffer_load_b64(rs, 0, 0, 0));
-        const int off = pred ? (int)(idx * 8u) : 0x7ffffff0;
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), rs, off, 0, 0);
-    }
     __device__ __forceinline__ void store(uint32_t idx, double v) const
     {
         using u2 = decltype(__builtin_amdgcn_raw_buffer_load_b64(rs, 0, 0, 0));
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), rs, (int)(idx * 8u), 0, 0);
     }
 };
-using GlobalTable = GlobalTableT<double>;
 template <typename V>
 struct LdsTableT {
     V *p;
     uint32_t base = 0;  // table index of p[0]
     __device__ __forceinline__ V load(uint32_t idx) const { return p[idx - base]; }
-    __device__ __forceinline__ void store_if(bool pred, uint32_t idx, V v) const
-    {
-        if (pred) p[idx - base] = v;
-    }
     __device__ __forceinline__ void store(uint32_t idx, V v) const { p[idx - base] = v; }
 };
-using LdsTable = LdsTableT<double>;
 
 // Ping-pong value layout (VAR 4): a middle layer t lives in buffer t & 1 at
 // the start of the slot instead of its own span, so the two live layers of
@@ -320,122 +297,13 @@ struct SplitTable {
     }
 };
 
-// acc[k] = min(acc[k], g + d[m][k+1]) for all k: one member of the source row.
-template <int N>
-__device__ __forceinline__ void relax_member(double (&acc)[N], const double *dl, int m, double g)
-{
-    const double2 *drow = reinterpret_cast<const double2 *>(__builtin_assume_aligned(dl + m * dist_stride(N), 16));
-#pragma unroll
-    for (int q = 0; q < N / 2; ++q) {
-        const double2 v = drow[q];
-        acc[2 * q] = fmin(acc[2 * q], g + v.x);
-        acc[2 * q + 1] = fmin(acc[2 * q + 1], g + v.y);
-    }
-    if constexpr (N & 1) acc[N - 1] = fmin(acc[N - 1], g + dl[m * dist_stride(N) + N - 1]);
-}
-
-// Store acc[k] for every k not in Tm at G[Tm+k][k] of layer S = T+1.
-// colex rank of T+{k} (e_i = members ascending, p = #members below k):
-//   sum_{i<p} C(e_i,i+1) + C(k,p+1) + sum_{i>=p} C(e_i,i+2)
-//   = r - s1 + C(k,p+1) + s2, with s1/s2 the suffix sums of C(e_i,i+1) /
-// C(e_i,i+2) over the members above k, built while k runs downwards.
-// Branch-free: two binomial lookups per k and a predicated store.
-template <int N, int S, typename Tab>
-__device__ __forceinline__ void scatter_row(const Tab &tab, const double (&acc)[N], uint32_t Tm, uint32_t r,
-                                            const int *binom)
-{
-    constexpr int T = S - 1;
-    constexpr uint32_t ROWS_S = cbinom(N, S);
-    constexpr uint32_t DST = layer_off(N, S);
-    int q = 0, s1 = 0, s2 = 0;
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {
-        const int in = (Tm >> k) & 1u;
-        const int p = T - q - in;
-        const int c1 = binom[k * kBinomStride + p + 1];
-        const int c2 = binom[k * kBinomStride + p + 2];
-        const uint32_t rank = r - (uint32_t)s1 + (uint32_t)c1 + (uint32_t)s2;
-        tab.store_if(!in, DST + (uint32_t)p * ROWS_S + rank, acc[k]);
-        s1 += in ? c1 : 0;
-        s2 += in ? c2 : 0;
-        q += in;
-    }
-}
-
-// Global table: layer T -> T+1, rows r = tid, tid+THREADS, ...; the next row's
-// t loads are in flight while the current row is swept.
-template <int N, int T, int THREADS>
-__device__ __forceinline__ void layer_pass_global(const GlobalTable &tab, const double *__restrict__ dl,
-                                                  const int *__restrict__ binom, double *__restrict__ slot,
-                                                  const uint32_t *__restrict__ masks, uint32_t tid)
-{
-    constexpr int S = T + 1;
-    constexpr uint32_t ROWS = cbinom(N, T);
-    constexpr uint32_t SRC = layer_off(N, T);
-    const uint32_t *mt = masks + mask_off(N, T);
-    uint32_t r = tid;
-    if (r >= ROWS) return;
-    double nxt[T];
-    uint32_t nmask = mt[r];
-#pragma unroll
-    for (int j = 0; j < T; ++j) nxt[j] = tab.load(SRC + j * ROWS + r);
-    for (; r < ROWS; r += THREADS) {
-        const uint32_t Tm = nmask;
-#pragma unroll
-        for (int j = 0; j < T; ++j) slot[j * THREADS] = nxt[j];
-        const uint32_t rn = r + THREADS;
-        if (rn < ROWS) {
-            nmask = mt[rn];
-#pragma unroll
-            for (int j = 0; j < T; ++j) nxt[j] = tab.load(SRC + j * ROWS + rn);
-        }
-        double acc[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) acc[k] = kIntMax;
-        uint32_t bits = Tm;
-#pragma unroll 2
-        for (int j = 0; j < T; ++j) {
-            const int m = __builtin_ctz(bits) + 1;
-            bits &= bits - 1u;
-            relax_member<N>(acc, dl, m, slot[j * THREADS]);
-        }
-        scatter_row<N, S>(tab, acc, Tm, r, binom);
-    }
-}
-
-// LDS table: the source row is read straight from the table.
-template <int N, int T, int THREADS>
-__device__ __forceinline__ void layer_pass_lds(const LdsTable &tab, const double *__restrict__ dl,
-                                               const int *__restrict__ binom, const uint32_t *__restrict__ masks,
-                                               uint32_t tid)
-{
-    constexpr int S = T + 1;
-    constexpr uint32_t ROWS = cbinom(N, T);
-    constexpr uint32_t SRC = layer_off(N, T);
-    const uint32_t *mt = masks + mask_off(N, T);
-    for (uint32_t r = tid; r < ROWS; r += THREADS) {
-        const uint32_t Tm = mt[r];
-        double acc[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) acc[k] = kIntMax;
-        uint32_t bits = Tm;
-#pragma unroll 2
-        for (int j = 0; j < T; ++j) {
-            const int m = __builtin_ctz(bits) + 1;
-            bits &= bits - 1u;
-            relax_member<N>(acc, dl, m, tab.load(SRC + j * ROWS + r));
-        }
-        scatter_row<N, S>(tab, acc, Tm, r, binom);
-    }
-}
-
 // Compact pass, layer T -> T+1: a thread owns source rows r = tid, tid+THREADS,
 // ... and relaxes ONLY the Q = N-T destinations k not in T (every row of a
 // layer has exactly Q of them, so the loops have static trip counts):
 //   acc[q] = min_j g[j] + d[m_j][k_q]           (m_j: j-th member, k_q: q-th non-member)
 //   G[T+k_q][k_q] = acc[q]  at  DST + (k_q - q) * C(N,T+1) + colexrank(T + k_q)
 // (k_q - q = number of members below k_q = position of k_q in T+k_q).
-// t*(N-t) relaxations per row instead of t*N for the member sweep: no lane
+// t*(N-t) relaxations per row instead of t*N for a sweep over all N cities: no lane
 // computes a value that is thrown away.  Registers: t + 2(N-t) + O(1) per
 // thread, so the kernel runs at 8 waves/SIMD without spilling.
 // PF (prefetch depth): the masks and t values of the next PF rows are in
@@ -577,28 +445,14 @@ __device__ __forceinline__ void all_layers_split(const SplitTable<V, N, A, PP> &
     }
 }
 
-template <int N, int T, int THREADS, typename Tab>
-__device__ __forceinline__ void all_layers(const Tab &tab, const double *dl, const int *binom, double *slot,
-                                           const uint32_t *masks, uint32_t tid)
-{
-    if constexpr (T < N) {
-        if constexpr (std::is_same<Tab, LdsTable>::value)
-            layer_pass_lds<N, T, THREADS>(tab, dl, binom, masks, tid);
-        else
-            layer_pass_global<N, T, THREADS>(tab, dl, binom, slot, masks, tid);
-        __syncthreads();
-        all_layers<N, T + 1, THREADS>(tab, dl, binom, slot, masks, tid);
-    }
-}
-
 // One workgroup solves blocks blockIdx.x, blockIdx.x + gridDim.x, ...
 // LDS_TABLE: the whole compact table lives in LDS (N <= 11), else in the
-// workgroup's global slot.  COMPACT selects the layer pass (see above).
-// Occupancy target (waves per SIMD): the member sweep holds N running minima
-// plus a prefetched row (<= 128 VGPRs, 4 waves); the compact pass needs about
-// half of that (<= 64 VGPRs, 8 waves) at the reference's sizes.
-// VAR: 0 member sweep, 1 compact, 2 compact + next-row prefetch, 3 compact + two rows prefetched,
-// 4 = 2 + ping-pong values + parent bytes
+// workgroup's global slot.
+// Occupancy target (waves per SIMD): the compact pass without prefetch needs
+// <= 64 VGPRs (8 waves) at the reference's sizes; the variants that hold a
+// prefetched row are compiled for 4 waves (<= 128 VGPRs): min_waves below.
+// VAR: 1 compact pass (the LDS-table kernels), 2 compact + next-row prefetch,
+// 4 = 2 + ping-pong values + parent words (global-table kernels)
 #ifndef TSPGPU_K1_V4_PF
 #define TSPGPU_K1_V4_PF 1  // rows prefetched by the variant-4 pass
 #endif
@@ -633,6 +487,8 @@ __global__ __launch_bounds__(THREADS, min_waves(N, VAR, THREADS)) void heldkarp_
     V *lds_rest = reinterpret_cast<V *>(smem + kBinomBytesPadded + dl_bytes(N, VB) + rank_lut_bytes(N));
     const int tid = threadIdx.x;
 
+    // (unread since the member sweep went; kept with its 2 KB so that no kept
+    // kernel's LDS layout or size changes: see lds_bytes)
     for (int i = tid; i < kBinomRows * kBinomStride; i += THREADS) binom[i] = info->binom[i];
     for (int i = tid; i < rank_lut_ints(N); i += THREADS) rl[i] = info->rlut[i];
 
@@ -642,8 +498,8 @@ __global__ __launch_bounds__(THREADS, min_waves(N, VAR, THREADS)) void heldkarp_
     else
         tab = slots + (size_t)blockIdx.x * slot_doubles;
     using Tab = typename std::conditional<LDS_TABLE, LdsTableT<V>, GlobalTableT<V>>::type;
-    // compact global kernels: the end layers live in LDS behind the LUT
-    constexpr int A = (!LDS_TABLE && VAR >= 1) ? lds_end_layers(N, THREADS, VB) : 0;
+    // global-table kernels: the end layers live in LDS behind the LUT
+    constexpr int A = !LDS_TABLE ? lds_end_layers(N, THREADS, VB) : 0;
     constexpr bool PP = VAR == 4 && !LDS_TABLE;
     SplitTable<V, N, A, PP> tb;
     tb.lo = lds_rest;
@@ -701,12 +557,10 @@ __global__ __launch_bounds__(THREADS, min_waves(N, VAR, THREADS)) void heldkarp_
         asm volatile("" : "+v"(tid_b));
         if constexpr (PP)
             all_layers_split<V, N, A, 1, THREADS, var_pf(VAR)>(tb, dl, rl, masks, (uint32_t)tid_b, par);
-        else if constexpr (!LDS_TABLE && VAR >= 1)
+        else if constexpr (!LDS_TABLE)
             all_layers_split<V, N, A, 1, THREADS, var_pf(VAR)>(tb, dl, rl, masks, (uint32_t)tid_b, NoParents{});
-        else if constexpr (VAR >= 1)
+        else
             all_layers_compact<V, N, 1, THREADS, var_pf(VAR)>(th, dl, rl, masks, (uint32_t)tid_b);
-        else if constexpr (std::is_same<V, double>::value)
-            all_layers<N, 1, THREADS>(th, dl, binom, lds_rest + tid_b, masks, (uint32_t)tid_b);
 
         // closing min (tsp.cpp:483-499) and backtracking, one wave: lane m-1
         // holds candidate m.  The state value of the next step is the g value
@@ -795,7 +649,7 @@ __global__ __launch_bounds__(THREADS, min_waves(N, VAR, THREADS)) void heldkarp_
 template <typename V, int N, bool LDS, int THREADS, int VAR>
 hipError_t launch_n(const LaunchArgs &a, int grid)
 {
-    const size_t lds = lds_bytes(N, LDS, THREADS, VAR >= 1, ValT<V>::bytes);
+    const size_t lds = lds_bytes(N, LDS, THREADS, ValT<V>::bytes);
     if (lds > 64 * 1024) {
         static bool raised = false;  // once per instantiation
         if (!raised) {
@@ -820,7 +674,8 @@ template <typename V, int N, int VAR>
 hipError_t launch_threads_v(const LaunchArgs &a, int grid)
 {
     if constexpr (N <= kLdsTableMaxN) {
-        if (a.use_lds) return launch_n<V, N, true, lds_table_threads(N), VAR >= 2 ? 1 : VAR>(a, grid);
+        // (the LDS-table kernels exist as VAR 1 only: the compact pass without prefetch)
+        if (a.use_lds) return launch_n<V, N, true, lds_table_threads(N), 1>(a, grid);
     }
     if constexpr (VAR == 4 && (N < 11 || N > 15)) {
         // ping-pong + parent words: 12..16 cities (4-bit parents, <= 14 per row)
@@ -837,13 +692,10 @@ hipError_t launch_threads_v(const LaunchArgs &a, int grid)
 template <int N>
 hipError_t launch_threads(const LaunchArgs &a, int grid)
 {
-    // integer matrices: the default (compact + prefetch) pass only
+    // (VAR 3, two rows in flight, measured no faster than one: not instantiated)
     if (a.vbytes == 4)
         return a.variant >= 4 ? launch_threads_v<int32_t, N, 4>(a, grid) : launch_threads_v<int32_t, N, 2>(a, grid);
-    // (VAR 3, two rows in flight, measured no faster than one: not instantiated)
-    if (a.variant >= 4) return launch_threads_v<double, N, 4>(a, grid);
-    if (a.variant >= 2) return launch_threads_v<double, N, 2>(a, grid);
-    return a.variant == 1 ? launch_threads_v<double, N, 1>(a, grid) : launch_threads_v<double, N, 0>(a, grid);
+    return a.variant >= 4 ? launch_threads_v<double, N, 4>(a, grid) : launch_threads_v<double, N, 2>(a, grid);
 }
 
 }  // namespace tspgpu

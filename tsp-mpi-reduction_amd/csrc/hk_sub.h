@@ -2,9 +2,11 @@
 //
 // Same recurrence, same IEEE operations, same first-strict-minimum argmin and
 // the same global slot layout (push area, parent words, recompute area) as
-// variant 5 (hk_tiled.h), whose backtracking kernel it reuses — so the same
-// cost and tour bits (tsp.cpp:424-499).  What changes is how a sub-cube's
-// passes are scheduled and where a relaxation's distance comes from:
+// its predecessor, variant 5, whose layout helpers and backtracking kernel
+// it reuses (hk_tiled.h; variant 5's forward kernel is in git history) — so
+// the same cost and tour bits (tsp.cpp:424-499).  What changed against
+// variant 5 is how a sub-cube's passes are scheduled and where a
+// relaxation's distance comes from:
 //
 // * Distances touching a high city need no address arithmetic.  The inner
 //   distance image in LDS has H extra rows and columns that hold, for the
@@ -842,8 +844,8 @@ __device__ __forceinline__ void sub_dispatch_last(const SubCtx<V, N, L> &c, uint
 }
 
 // Forward pass + closing min of blocks blk0 + blockIdx.x, +gridDim.x, ...;
-// writes cost_out[blk] and the tour's last inner city (tour[n-1]) like
-// hk_tiled_kernel; hk_tiled_backtrack completes the tour from the slot.
+// writes cost_out[blk] and the tour's last inner city (tour[n-1]);
+// hk_tiled_backtrack (hk_tiled.h) completes the tour from the slot.
 template <typename V, int N, int L, int THREADS, int WG>
 __global__ __launch_bounds__(THREADS, tiled_waves(THREADS, WG)) void hk_sub_kernel(
     const V *__restrict__ dist, int nblocks, int blk0, char *__restrict__ slots, uint32_t slot_bytes,

@@ -1,4 +1,5 @@
-// K1 variant 5 — "sub-cube" tiled Held-Karp for gfx950 (MI355X).
+// K1 "sub-cube" Held-Karp: the table layout, the per-block slot format and the
+// backtracking kernel that the forward kernel of variant 6 (hk_sub.h) builds on.
 //
 // Same recurrence, same IEEE operations and the same first-strict-minimum
 // argmin as heldkarp_impl.h (tsp.cpp:424-499), so the same cost and tour bits;
@@ -20,28 +21,22 @@
 // instead of 3.93 MB (SURVEY.md §8(d)'s compulsory bytes of the
 // layer-by-layer form).
 //
-// Row-owner pass (h, j): a thread owns a source row T = h<<L | l, |l| = j,
-// t = |h|+j members, Q = N-t non-members; for every non-member k it computes
-//   acc[k] = min over members m of G[T][m] + d[m][k]
-// (the values of tsp.cpp:457-470) and stores acc[k] to the next LDS layer (k
-// low) or to the push area of sub-cube h|k (k high).  The argmin (the
-// reference's first strict minimum over members ascending) is kept only for
-// the top rows (>= N - TSPGPU_TILED_TA_OFF members: one 64-bit word of 4-bit
-// parents per row); everywhere else the pass is min-only — two VALU
-// instructions per relaxation instead of four.  The backtracking kernel
-// (hk_tiled_backtrack, one wave per block, all blocks at once) follows the
-// parent words down to that size, then recomputes the few rows the path still
-// needs from the block's pushed values (only subsets of the path's row, 2-8%
-// of the forward relaxations) and takes the same first strict minimum of the
-// same candidates — so the same tour bits.  At n = 16: 7.4 ms forward + 0.7 ms
-// backtracking per 16384 blocks, against 9.6 ms with the argmin everywhere
-// (profiles/r02/k1_argmin_threshold.txt).
+// Slot of one block (global memory, tiled_slot_bytes): the push area
+// [h][high city][row], the parent words [h][row] and the backtracking's
+// recompute area.  The forward kernel keeps the argmin (the reference's first
+// strict minimum over members ascending) only for the top rows (>= N -
+// TSPGPU_TILED_TA_OFF members: one 64-bit word of 4-bit parents per row);
+// everywhere else its pass is min-only — two VALU instructions per relaxation
+// instead of four.  The backtracking kernel (hk_tiled_backtrack, one wave per
+// block, all blocks at once) follows the parent words down to that size, then
+// recomputes the few rows the path still needs from the block's pushed values
+// (only subsets of the path's row, 2-8% of the forward relaxations) and takes
+// the same first strict minimum of the same candidates — so the same tour
+// bits (profiles/r02/k1_argmin_threshold.txt).
 //
-// Distances: the N x N inner matrix in LDS with an odd row stride
-// (kTiledDS = 19 entries), optionally replicated R times (element e of copy c
-// at 8*(e*R + c), lane uses copy lane % R).  The product configurations use
-// R = 1: replication R = 2..32 measured within +-1% (k1_cfg.h,
-// profiles/r02/k1_tiled_v*.log).
+// The forward kernel this file was written for, variant 5 (a row-owner pass
+// per (h, j)), lost to variant 6 at every size and was last in commit
+// 8f46298; DESIGN.md §4.0 keeps its measurements.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -71,18 +66,6 @@ constexpr int kTiledDS = TSPGPU_TILED_DS;
 #ifndef TSPGPU_TILED_TA_OFF
 #define TSPGPU_TILED_TA_OFF 4
 #endif
-#ifndef TSPGPU_TILED_QC
-#define TSPGPU_TILED_QC 7  // destinations relaxed together (register budget of a chunk)
-#endif
-#ifndef TSPGPU_TILED_AHEAD
-#define TSPGPU_TILED_AHEAD 6  // d loads in flight per lane in the relaxation loop
-#endif
-// Measured and not kept (profiles/r02; the switches were removed in round
-// 6): the high distance rows/columns permuted into sub-cube order between
-// sub-cubes (the passes 3% faster, the permutation on wave 0's path 6% slower
-// — variant 6 does it on idle threads instead, hk_sub.h) and
-// destination-parallel edge passes (spills; variant 6 has them in a form that
-// does not spill).
 
 // host-built tables of one L (device copy, staged into LDS per workgroup)
 struct TiledInfo {
@@ -105,19 +88,6 @@ __host__ __device__ constexpr int tiled_region_vals(int L)
         m = s > m ? s : m;
     }
     return m;
-}
-__host__ __device__ constexpr size_t tiled_lds_bytes(int N, int L, int R, int vb, bool tables = true)
-{
-    return (size_t)N * kTiledDS * R * vb     // replicated inner distances, rows of kTiledDS
-           + (size_t)2 * 16 * vb             // d[0][k], d[m][0]
-           + (size_t)tiled_region_vals(L) * vb  // live low layers
-           + (tables ? (size_t)2 * 2 * (1 << L) : 0);  // mask + rank (u16), unless read from global
-}
-// the mask/rank tables stay in global memory (L1/L2-resident) when staging
-// them in LDS would keep WG workgroups from fitting a CU's 160 KB
-__host__ __device__ constexpr bool tiled_global_tables(int N, int L, int R, int vb, int wg)
-{
-    return tiled_lds_bytes(N, L, R, vb, true) * wg > 160 * 1024;
 }
 // push area of one slot: [h][c][idx] values (c = high city index 0..H-1,
 // idx = the row's place in the sorted L-bit mask list)
@@ -267,8 +237,8 @@ __device__ __forceinline__ void relax_min(int32_t &acc, int32_t g, int32_t d)
 
 template <typename V, int N, int L, int R>
 struct TiledCtx {
-    const V *dr;               // LDS replicated distances
-    const uint16_t *lmask;     // sorted L-bit masks (LDS, or global: tiled_global_tables)
+    const V *dr;               // LDS distances, rows of kTiledDS entries, R copies each (R = 1 in use)
+    const uint16_t *lmask;     // sorted L-bit masks (LDS)
     const uint16_t *lrankb;    // colex rank x sizeof(V) (byte offset inside a position column)
     V *region;                 // LDS live low layers
     Rsrc<V> push;              // this slot's push area
@@ -276,153 +246,6 @@ struct TiledCtx {
     Rsrc<V> rec;               // this slot's backtracking recompute area
     const int *moff;           // first index of each popcount class (backtracking)
 };
-
-// One pass (h, J) of a sub-cube: T = |h| + J members per source row, all
-// counts static (one instantiation per (T, J)), so the split of members and
-// non-members into low (per lane) and high (uniform) parts costs no branch.
-template <typename V, int N, int L, int T, int J, int THREADS, int R>
-__device__ __forceinline__ void tiled_pass(const TiledCtx<V, N, L, R> &c, uint32_t h, uint32_t tid)
-{
-    constexpr int H = N - L;
-    constexpr int Q = N - T;
-    constexpr int HC = T - J;   // high members (uniform)
-    constexpr int QL = L - J;   // low non-members (per lane), listed first
-    constexpr int QH = Q - QL;  // high non-members (uniform)
-    static_assert(HC >= 0 && HC <= H && QL >= 0 && QH >= 0 && T >= 1 && T < N, "bad pass");
-    constexpr int NL = 1 << L;
-    constexpr int VB = sizeof(V);
-    constexpr int ROWS = cbinom(L, J);
-    constexpr int BASE = tiled_moff(L, J);
-    constexpr int ROWS_N = J < L ? cbinom(L, J + 1) : 0;
-    constexpr int REGV = tiled_region_vals(L);
-    constexpr int CUR = (J & 1) ? REGV - ROWS * J : 0;
-    constexpr int NXT = ((J + 1) & 1) ? REGV - ROWS_N * (J + 1) : 0;
-    // argmin and parent word only for the top rows (tiled_backtrack recomputes
-    // the rest)
-    constexpr bool ARG = T >= N - TSPGPU_TILED_TA_OFF;
-    // distance rows of kTiledDS entries (R copies each): a member's row
-    // offset is bit * DROW, a non-member's column offset bit << SK; the argmin
-    // is kept as the member's row offset (one register less per member) and
-    // turned back into the bit by a division by the constant DROW
-    constexpr int SK = __builtin_ctz((unsigned)(R * VB));
-    constexpr uint32_t DROW = (uint32_t)(kTiledDS * R * VB);
-    static_assert((R & (R - 1)) == 0 && N < kTiledDS, "R must be a power of two");
-    // uniform: the high members and high non-members of h, ascending
-    uint32_t hm[HC > 0 ? HC : 1], hn[QH > 0 ? QH : 1];
-    {
-        uint32_t hb = h;
-#pragma unroll
-        for (int i = 0; i < HC; ++i) {
-            hm[i] = __builtin_ctz(hb);
-            hb &= hb - 1u;
-        }
-        uint32_t nb = ~h & ((1u << H) - 1u);
-#pragma unroll
-        for (int i = 0; i < QH; ++i) {
-            hn[i] = __builtin_ctz(nb);
-            nb &= nb - 1u;
-        }
-    }
-    const uint32_t lane_off = (tid & (uint32_t)(R - 1)) * VB;
-    const char *drb = reinterpret_cast<const char *>(c.dr);
-    char *lds_nxt = reinterpret_cast<char *>(c.region + NXT);
-    for (uint32_t r = tid; r < (uint32_t)ROWS; r += THREADS) {
-        const uint32_t l = c.lmask[BASE + r];
-        const uint32_t voff = (BASE + r) * VB;   // row offset in a push column
-        // the row's T values: low members from LDS, high members from the pushes
-        V g[T];
-#pragma unroll
-        for (int p = 0; p < J; ++p) g[p] = c.region[CUR + p * ROWS + r];
-#pragma unroll
-        for (int i = 0; i < HC; ++i) g[J + i] = c.push.load(voff, (h * H + hm[i]) * (uint32_t)(NL * VB));
-        // members ascending (low bits of l, then the high members of h)
-        uint32_t mrow[T];
-        uint32_t lb = l;
-#pragma unroll
-        for (int p = 0; p < J; ++p) {
-            mrow[p] = (uint32_t)__builtin_ctz(lb) * DROW + lane_off;
-            lb &= lb - 1u;
-        }
-#pragma unroll
-        for (int i = 0; i < HC; ++i) mrow[J + i] = (L + hm[i]) * DROW + lane_off;
-        // Destinations in chunks of at most TSPGPU_TILED_QC (registers: acc,
-        // arg and the column offsets of one chunk only); the non-members come
-        // ascending (low non-members of l, then those of h).  Per chunk: the
-        // T*QC relaxations, member-major (members ascending for every
-        // destination), each d value loaded TSPGPU_TILED_AHEAD relaxations
-        // ahead; a scheduling barrier per relaxation keeps the compiler from
-        // hoisting all loads (and their registers) up front.  The first
-        // member initialises acc/arg: with validated inputs every candidate is
-        // below the reference's INT_MAX start value (tsp.cpp:453), so its
-        // first comparison always succeeds.
-        uint32_t nb = ~l & (uint32_t)(NL - 1);
-        uint32_t wlo = 0, whi = 0;
-        constexpr int QC = TSPGPU_TILED_QC;
-        static_for<(Q + QC - 1) / QC>([&](auto ci) {
-            constexpr int C0 = decltype(ci)::value * QC;
-            constexpr int QN = Q - C0 < QC ? Q - C0 : QC;
-            uint32_t kof[QN];
-#pragma unroll
-            for (int qq = 0; qq < QN; ++qq) {
-                const int q = C0 + qq;
-                if (q < QL) {
-                    kof[qq] = (uint32_t)__builtin_ctz(nb) << SK;
-                    nb &= nb - 1u;
-                } else {  // high non-member q - QL
-                    kof[qq] = (L + hn[q - QL]) << SK;
-                }
-            }
-            V acc[QN];
-            uint32_t arg[ARG ? QN : 1];
-            {
-                constexpr int TQ = T * QN;
-                constexpr int AH = TSPGPU_TILED_AHEAD < TQ ? TSPGPU_TILED_AHEAD : TQ;
-                V dv[AH];
-#pragma unroll
-                for (int i = 0; i < AH; ++i) dv[i] = *reinterpret_cast<const V *>(drb + mrow[i / QN] + kof[i % QN]);
-#pragma unroll
-                for (int i = 0; i < TQ; ++i) {
-                    const V d = dv[i % AH];
-                    if (i + AH < TQ)
-                        dv[i % AH] = *reinterpret_cast<const V *>(drb + mrow[(i + AH) / QN] + kof[(i + AH) % QN]);
-                    if (i < QN) {
-                        acc[i] = g[0] + d;
-                        if constexpr (ARG) arg[i] = mrow[0];
-                    } else {
-                        if constexpr (ARG)
-                            relax_argmin(acc[i % QN], arg[i % QN], g[i / QN], d, mrow[i / QN]);
-                        else
-                            relax_min(acc[i % QN], g[i / QN], d);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int qq = 0; qq < QN; ++qq) {
-                const int q = C0 + qq;
-                if (q < QL) {
-                    // low k -> next LDS layer (position k - q, colex rank of l + k)
-                    const uint32_t k = kof[qq] >> SK;
-                    const uint32_t rb = c.lrankb[l | (1u << k)];
-                    *reinterpret_cast<V *>(lds_nxt + (k - (uint32_t)q) * (uint32_t)(ROWS_N * VB) + rb) = acc[qq];
-                } else {
-                    // high k -> the push column (h | k, k) of sub-cube h | k, same row index
-                    const uint32_t cb = hn[q - QL];
-                    c.push.store(voff, ((h | (1u << cb)) * H + cb) * (uint32_t)(NL * VB), acc[qq]);
-                }
-                // the row's parent word: nibble q = bit index of the argmin member
-                if constexpr (ARG) {
-                    const uint32_t pos = arg[qq] / DROW;  // table row of the argmin member = its city bit
-                    if (q < 8)
-                        wlo |= pos << (4 * q);
-                    else
-                        whi |= pos << (4 * (q - 8));
-                }
-            }
-        });
-        if constexpr (ARG) c.par.store((BASE + r) * 8u, h * (uint32_t)(NL * 8), ((uint64_t)whi << 32) | wlo);
-    }
-}
 
 __host__ __device__ constexpr int pow2_at_least(int q)
 {
@@ -573,137 +396,8 @@ __device__ bool tiled_backtrack(const TiledCtx<V, N, L, R> &c, const V *d0, int 
     return ok;
 }
 
-template <typename V, int N, int L, int J, int THREADS, int R>
-__device__ __forceinline__ void tiled_dispatch_h(const TiledCtx<V, N, L, R> &c, uint32_t h, int hc, uint32_t tid)
-{
-    constexpr int H = N - L;
-#define TSPGPU_TP(HC)                                                                      \
-    case HC:                                                                               \
-        if constexpr (HC <= H && J + HC >= 1 && J + HC < N)                                \
-            tiled_pass<V, N, L, J + HC, J, THREADS, R>(c, h, tid);                         \
-        break;
-    switch (hc) {
-        TSPGPU_TP(0) TSPGPU_TP(1) TSPGPU_TP(2) TSPGPU_TP(3) TSPGPU_TP(4) TSPGPU_TP(5) TSPGPU_TP(6)
-        TSPGPU_TP(7)
-    default: break;
-    }
-#undef TSPGPU_TP
-}
-
-template <typename V, int N, int L, int THREADS, int R>
-__device__ __forceinline__ void tiled_dispatch(const TiledCtx<V, N, L, R> &c, uint32_t h, int hc, int j, uint32_t tid)
-{
-#define TSPGPU_TJ(JJ)                                                                      \
-    case JJ:                                                                               \
-        if constexpr (JJ <= L) tiled_dispatch_h<V, N, L, JJ, THREADS, R>(c, h, hc, tid);   \
-        break;
-    switch (j) {
-        TSPGPU_TJ(0) TSPGPU_TJ(1) TSPGPU_TJ(2) TSPGPU_TJ(3) TSPGPU_TJ(4) TSPGPU_TJ(5) TSPGPU_TJ(6)
-        TSPGPU_TJ(7) TSPGPU_TJ(8) TSPGPU_TJ(9) TSPGPU_TJ(10) TSPGPU_TJ(11) TSPGPU_TJ(12)
-    default: break;
-    }
-#undef TSPGPU_TJ
-}
-
+// waves per SIMD of a forward kernel with wg_per_cu workgroups of `threads` on a CU (__launch_bounds__)
 __host__ __device__ constexpr int tiled_waves(int threads, int wg_per_cu) { return threads * wg_per_cu / 256; }
-
-// Forward pass + closing min of blocks blk0 + blockIdx.x, +gridDim.x, ...;
-// writes cost_out[blk] and the tour's last inner city (tour[n-1]).  Every
-// block has its own global slot, kept for hk_tiled_backtrack.
-template <typename V, int N, int L, int THREADS, int R, int WG>
-__global__ __launch_bounds__(THREADS, tiled_waves(THREADS, WG)) void hk_tiled_kernel(
-    const V *__restrict__ dist, int nblocks, int blk0, char *__restrict__ slots, uint32_t slot_bytes,
-    const TiledInfo *__restrict__ info, V *__restrict__ cost_out, int32_t *__restrict__ tour_out)
-{
-    constexpr int H = N - L;
-    constexpr int NH = 1 << H;
-    constexpr int NL = 1 << L;
-    constexpr int n = N + 1;
-    constexpr int VB = sizeof(V);
-    static_assert(H <= 7, "tiled_dispatch_h covers at most 7 high cities");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    V *dr = reinterpret_cast<V *>(smem);
-    V *d0 = dr + N * kTiledDS * R;  // d[0][k], k = 1..N at [k-1]
-    V *dc = d0 + 16;                // d[m][0], m = 1..N at [m-1]
-    V *region = dc + 16;
-    constexpr bool GT = tiled_global_tables(N, L, R, VB, WG);
-    uint16_t *lmask = reinterpret_cast<uint16_t *>(region + tiled_region_vals(L));
-    uint16_t *lrankb = lmask + NL;
-    const uint32_t tid = threadIdx.x;
-
-    if constexpr (!GT) {
-        for (int i = tid; i < NL; i += THREADS) {
-            lmask[i] = info->mask[i];
-            lrankb[i] = VB == 8 ? info->rankb8[i] : info->rankb4[i];
-        }
-    }
-    TiledCtx<V, N, L, R> c;
-    c.dr = dr;
-    c.lmask = GT ? info->mask : lmask;
-    c.lrankb = GT ? (VB == 8 ? info->rankb8 : info->rankb4) : lrankb;
-    c.region = region;
-    c.moff = nullptr;  // (backtracking only)
-
-    for (int blk = blk0 + blockIdx.x; blk < nblocks; blk += gridDim.x) {
-        char *slot = slots + (size_t)(blk - blk0) * slot_bytes;
-        c.push.rs = uniform_rsrc(slot, (uint32_t)tiled_push_bytes(N, L, VB));
-        c.par.rs = uniform_rsrc(slot + tiled_push_bytes(N, L, VB), (uint32_t)tiled_parent_bytes(N, L));
-        const V *dsrc = dist + (size_t)blk * n * n;
-        for (int i = tid; i < N * kTiledDS * R; i += THREADS) {
-            const int e = i / R, m = e / kTiledDS, k = e % kTiledDS;  // columns >= N unused
-            dr[i] = k < N ? dsrc[(m + 1) * n + (k + 1)] : V(0);
-        }
-        if (tid < N) {
-            d0[tid] = dsrc[tid + 1];
-            dc[tid] = dsrc[(tid + 1) * n];
-        }
-        __syncthreads();
-        // layer 1: G[{i}][i] = d[0][i] (tsp.cpp:435's d[0][i] term): low i in
-        // sub-cube 0's first LDS layer (colex rank of {i} is i), high i pushed
-        // to sub-cube {i} at row idx 0 (the empty low part)
-        // (layer 1 is odd: it sits at the top of the region, regv - C(L,1))
-        if (tid < L) region[tiled_region_vals(L) - L + tid] = d0[tid];
-        if (tid < H) c.push.store(0, (((1u << tid) * H + tid) * NL) * VB, d0[L + tid]);
-        __syncthreads();
-
-        for (uint32_t h = 0; h < (uint32_t)NH; ++h) {
-            const int hc = __builtin_popcount(h);
-            const int j0 = h == 0 ? 1 : 0;
-            const int j1 = h == (uint32_t)(NH - 1) ? L - 1 : L;
-            for (int j = j0; j <= j1; ++j) {
-                tiled_dispatch<V, N, L, THREADS, R>(c, h, hc, j, tid);
-                if (j < j1) lds_barrier();
-            }
-            // pushes of this sub-cube are read by later ones: full barrier
-            __syncthreads();
-        }
-
-        // closing min (tsp.cpp:483-499): G[full][m] + d[m][0], first strict min
-        if (tid < 64) {
-            const int m = tid + 1;
-            const bool valid = m <= N;
-            V gl = V(0);
-            if (valid) {
-                if (m <= L)  // low layer L: one row, position m-1
-                    gl = region[((L & 1) ? tiled_region_vals(L) - L : 0) + (m - 1)];
-                else
-                    gl = c.push.load((NL - 1) * VB, ((uint32_t)((NH - 1) * H + (m - 1 - L)) * NL) * VB);
-            }
-            const V cand = valid ? gl + dc[m - 1] : ValT<V>::invalid;
-            const V best = ValT<V>::vmin(wave_min(cand), ValT<V>::inf);
-            const unsigned long long hit = __ballot(valid && cand == best && cand < ValT<V>::inf);
-            const int bestM = hit ? __ffsll(hit) : 0;
-            if (tid == 0) {
-                int32_t *tour = tour_out + (size_t)blk * (n + 1);
-                tour[0] = 0;
-                tour[n - 1] = bestM;
-                tour[n] = 0;
-                cost_out[blk] = bestM ? best : V(-1);
-            }
-        }
-        __syncthreads();
-    }
-}
 
 // Backtracking (tiled_backtrack): one wave per block, four per workgroup,
 // persistent over the blocks of the launch.  A block's backtracking is a chain
@@ -761,42 +455,5 @@ __global__ __launch_bounds__(64 * kTiledBtWaves, TSPGPU_TILED_BTWG) void hk_tile
     }
 }
 }  // namespace
-
-struct TiledArgs {
-    const void *dist;
-    int n, blk0, blk1;        // blocks [blk0, blk1) of this launch pair
-    char *slots;              // one slot per block of [blk0, blk1)
-    uint32_t slot_bytes;
-    const TiledInfo *info;
-    void *cost;
-    int32_t *tour;
-    int grid;
-    int bt_grid;              // backtracking workgroups (kTiledBtWaves blocks each at a time)
-    hipStream_t stream;
-    hipEvent_t ev_mid;        // recorded between the two kernels when non-null (split timing)
-};
-
-template <typename V, int N, int L, int THREADS, int R, int WG>
-hipError_t launch_tiled_n(const TiledArgs &a)
-{
-    const size_t lds = tiled_lds_bytes(N, L, R, sizeof(V), !tiled_global_tables(N, L, R, sizeof(V), WG));
-    static bool raised = false;  // once per instantiation
-    if (!raised) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hk_tiled_kernel<V, N, L, THREADS, R, WG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        raised = true;
-    }
-    hipLaunchKernelGGL((hk_tiled_kernel<V, N, L, THREADS, R, WG>), dim3(a.grid), dim3(THREADS), lds, a.stream,
-                       static_cast<const V *>(a.dist), a.blk1, a.blk0, a.slots, a.slot_bytes, a.info,
-                       static_cast<V *>(a.cost), a.tour);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && a.ev_mid) e = hipEventRecord(a.ev_mid, a.stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((hk_tiled_backtrack<V, N, L>), dim3(a.bt_grid), dim3(64 * kTiledBtWaves), 0, a.stream, a.blk1, a.blk0,
-                       a.slots, a.slot_bytes, a.info, static_cast<const V *>(a.dist), static_cast<V *>(a.cost),
-                       a.tour);
-    return hipGetLastError();
-}
 
 }  // namespace tspgpu

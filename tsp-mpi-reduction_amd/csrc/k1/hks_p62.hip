@@ -1,4 +1,4 @@
-// K1 variant 6 configuration 62 (k1_cfg.h, tools/gen_k1_cfgs.py)
+// K1 variant 6 configuration 62 (a row of k1_cfg.h)
 #include "hk_sub.h"
 namespace tspgpu {
 template hipError_t launch_sub_n<double, 14, 10, 256, 6>(const SubArgs &);

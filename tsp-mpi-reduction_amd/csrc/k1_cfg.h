@@ -1,14 +1,18 @@
-// K1 large-batch configurations — GENERATED by tools/gen_k1_cfgs.py, edit there.
-//   TSPGPU_TILED_CFGS: variant 5 (hk_tiled.h)  X(id, value type, N, L, threads, distance copies R, workgroups/CU)
-//   TSPGPU_SUB_CFGS:   variant 6 (hk_sub.h)    X(id, value type, N, L, threads, workgroups/CU)
-// The first row per (N, value type) is the default; the *_SWEEP_* rows exist
-// only in a measurement build (make K1_SWEEP=1 -> TSPGPU_K1_SWEEP).
+// K1 large-batch configurations of variant 6 (hk_sub.h):
+//   X(id, value type, N, L, threads, workgroups/CU)
+// The first row per (N, value type) is the default; TSPGPU_TILED_CFG picks
+// another by id.  A new row needs a matching k1/hks_p<id>.hip.
+//
+// tests/test_k1_variants_gpu.py lists the configurations by reading this
+// file: it finds a table by its #define line and takes the rows up to the
+// next blank line.  The test suite of the commit before variant 5 was retired
+// (8f46298) must keep running against this library, and it looks up both
+// names below, so variant 5's keeps an empty table until that suite no
+// longer has to run.
 #pragma once
 #include "hk_sub.h"
-#include "hk_tiled.h"
 
-#define TSPGPU_TILED_PRODUCT_CFGS(X) \
-    /* none */
+#define TSPGPU_TILED_PRODUCT_CFGS(X) /* variant 5: retired, no rows */
 
 #define TSPGPU_SUB_PRODUCT_CFGS(X) \
     X(60, double, 15, 10, 256, 6) \
@@ -17,65 +21,19 @@
     X(63, double, 13, 10, 256, 6) \
     X(64, double, 12, 10, 256, 6)
 
-#ifdef TSPGPU_K1_SWEEP
-#define TSPGPU_TILED_SWEEP_CFGS(X) \
-    X(14, double, 15, 10, 256, 1, 6) \
-    X(20, int32_t, 15, 10, 256, 1, 8) \
-    X(22, double, 14, 10, 256, 1, 6) \
-    X(23, double, 13, 10, 256, 1, 6) \
-    X(26, double, 12, 10, 256, 1, 6) \
-    X(12, double, 15, 10, 256, 1, 5) \
-    X(2, double, 15, 11, 256, 1, 3) \
-    X(15, double, 15, 9, 256, 1, 6) \
-    X(19, int32_t, 15, 10, 256, 1, 6)
-
-#define TSPGPU_SUB_SWEEP_CFGS(X) \
-    X(71, double, 15, 9, 128, 12) \
-    X(72, int32_t, 15, 9, 128, 12) \
-    X(73, int32_t, 15, 9, 128, 16) \
-    X(65, double, 15, 10, 256, 5) \
-    X(66, int32_t, 15, 10, 256, 6) \
-    X(67, double, 15, 9, 256, 6) \
-    X(68, int32_t, 14, 10, 256, 8) \
-    X(69, int32_t, 13, 10, 256, 8) \
-    X(70, double, 15, 10, 256, 4)
-#else
-#define TSPGPU_TILED_SWEEP_CFGS(X)
-#define TSPGPU_SUB_SWEEP_CFGS(X)
-#endif
-
-#define TSPGPU_TILED_CFGS(X) TSPGPU_TILED_PRODUCT_CFGS(X) TSPGPU_TILED_SWEEP_CFGS(X)
-#define TSPGPU_SUB_CFGS(X) TSPGPU_SUB_PRODUCT_CFGS(X) TSPGPU_SUB_SWEEP_CFGS(X)
-
 namespace tspgpu {
-struct TiledCfg {
-    int id, vbytes, N, L, threads, R, wg;
-    hipError_t (*launch)(const TiledArgs &);
-};
 struct SubCfg {
     int id, vbytes, N, L, threads, wg;
     hipError_t (*launch)(const SubArgs &);
 };
-#define TSPGPU_TILED_EXTERN(ID, V, N, L, T, R, W) \
-    extern template hipError_t launch_tiled_n<V, N, L, T, R, W>(const TiledArgs &);
 #define TSPGPU_SUB_EXTERN(ID, V, N, L, T, W) extern template hipError_t launch_sub_n<V, N, L, T, W>(const SubArgs &);
-TSPGPU_TILED_CFGS(TSPGPU_TILED_EXTERN)
-TSPGPU_SUB_CFGS(TSPGPU_SUB_EXTERN)
-#undef TSPGPU_TILED_EXTERN
+TSPGPU_SUB_PRODUCT_CFGS(TSPGPU_SUB_EXTERN)
 #undef TSPGPU_SUB_EXTERN
 // every compiled configuration (tspgpu.cpp picks by n, value type and TSPGPU_TILED_CFG)
-inline const TiledCfg *tiled_cfgs(int *count)
-{
-#define TSPGPU_TILED_ROW(ID, V, N, L, T, R, W) {ID, (int)sizeof(V), N, L, T, R, W, &launch_tiled_n<V, N, L, T, R, W>},
-    static const TiledCfg t[] = {TSPGPU_TILED_CFGS(TSPGPU_TILED_ROW) {0, 0, 0, 0, 0, 0, 0, nullptr}};
-#undef TSPGPU_TILED_ROW
-    *count = (int)(sizeof(t) / sizeof(t[0])) - 1;  // (the last row only keeps the array non-empty)
-    return t;
-}
 inline const SubCfg *sub_cfgs(int *count)
 {
 #define TSPGPU_SUB_ROW(ID, V, N, L, T, W) {ID, (int)sizeof(V), N, L, T, W, &launch_sub_n<V, N, L, T, W>},
-    static const SubCfg t[] = {TSPGPU_SUB_CFGS(TSPGPU_SUB_ROW)};
+    static const SubCfg t[] = {TSPGPU_SUB_PRODUCT_CFGS(TSPGPU_SUB_ROW)};
 #undef TSPGPU_SUB_ROW
     *count = (int)(sizeof(t) / sizeof(t[0]));
     return t;

@@ -179,7 +179,7 @@ int ensure_tiled_info(tspgpu_ctx *c, int L)
     return 0;
 }
 
-// Variants 5/6 keep one global slot per block of a launch (1.65 MB at
+// Variant 6 keeps one global slot per block of a launch (1.65 MB at
 // n = 16) until its backtracking kernel has run, so a launch takes blocks in
 // chunks: up to 65536 (108 GB of the 288 GB at n = 16 — a persistent grid of
 // 1536 workgroups then idles a third of the chip for 0.67 of 42.7 rounds
@@ -306,9 +306,8 @@ int solve_sub(tspgpu_ctx *c, const SubCfg *cfg, const void *d_dist, int n, int n
     if (rc) return rc;
     // (TSPGPU_WG_PER_CU: measurement builds with another occupancy, hk_sub.h)
     const int grid = std::min(nblocks, c->cu_count * (c->wg_per_cu > 0 ? c->wg_per_cu : cfg->wg));
-    // variant 5's per-block slot (push area, parent words, recompute area,
-    // large enough for either backtracking kernel), kept until the
-    // backtracking kernel has run
+    // the per-block slot (push area, parent words, recompute area:
+    // hk_tiled.h), kept until the backtracking kernel has run
     const size_t slot = sub_slot_bytes(N, L, cfg->vbytes);
     int chunk = 0;
     if ((rc = ensure_slots(c, nblocks, slot, &chunk))) return rc;
@@ -336,62 +335,6 @@ int solve_sub(tspgpu_ctx *c, const SubCfg *cfg, const void *d_dist, int n, int n
     }
     c->last_grid = grid;
     c->last_variant = 6;
-    return 0;
-}
-
-// K1 variant 5 (sub-cube tiled, hk_tiled.h) configuration for (N, value
-// bytes): TSPGPU_TILED_CFG / c->tiled_cfg, else the measured default; null if
-// none exists for this size.
-const TiledCfg *pick_tiled(const tspgpu_ctx *c, int N, int vbytes)
-{
-    int cnt = 0;
-    const TiledCfg *t = tiled_cfgs(&cnt);
-    if (c->tiled_cfg >= 0) {
-        for (int i = 0; i < cnt; ++i)
-            if (t[i].id == c->tiled_cfg && t[i].N == N && t[i].vbytes == vbytes) return &t[i];
-        return nullptr;
-    }
-    for (int i = 0; i < cnt; ++i)  // first row of the table for this size is the default
-        if (t[i].N == N && t[i].vbytes == vbytes) return &t[i];
-    return nullptr;
-}
-
-int solve_tiled(tspgpu_ctx *c, const TiledCfg *cfg, const void *d_dist, int n, int nblocks, void *d_cost,
-                int32_t *d_tour, hipStream_t stream)
-{
-    const int N = n - 1, L = cfg->L;
-    int rc = ensure_tiled_info(c, L);
-    if (rc) return rc;
-    const int grid = std::min(nblocks, c->cu_count * cfg->wg);
-    // one global slot per block (push area, parent words of the top rows,
-    // backtracking recompute area: 1.65 MB at n = 16, hk_tiled.h), kept until
-    // the backtracking kernel of the launch has run (ensure_slots: chunks)
-    const size_t slot = tiled_slot_bytes(N, L, cfg->vbytes);
-    int chunk = 0;
-    if ((rc = ensure_slots(c, nblocks, slot, &chunk))) return rc;
-    for (int b0 = 0; b0 < nblocks; b0 += chunk) {
-        TiledArgs a{};
-        size_t ev0 = 0;
-        if ((rc = split_begin(c, stream, &ev0))) return rc;
-        a.ev_mid = c->split_timing ? c->ev_split[ev0 + 1] : nullptr;
-        a.dist = d_dist;
-        a.n = n;
-        a.blk0 = b0;
-        a.blk1 = std::min(nblocks, b0 + chunk);
-        a.slots = c->d_tslots;
-        a.slot_bytes = (uint32_t)slot;
-        a.info = static_cast<const TiledInfo *>(c->d_tinfo[L]);
-        a.cost = d_cost;
-        a.tour = d_tour;
-        a.grid = std::min(grid, a.blk1 - a.blk0);
-        a.bt_grid = std::min((a.blk1 - a.blk0 + kTiledBtWaves - 1) / kTiledBtWaves, c->cu_count * TSPGPU_TILED_BTWG);
-        a.stream = stream;
-        hipError_t e = cfg->launch(a);
-        if (e != hipSuccess) return hip_err(e);
-        if (c->split_timing && hipEventRecord(c->ev_split[ev0 + 2], stream) != hipSuccess) return -EIO;
-    }
-    c->last_grid = grid;
-    c->last_variant = 5;
     return 0;
 }
 
@@ -464,35 +407,26 @@ int solve_device_unordered(tspgpu_ctx *c, const void *d_dist, int n, int nblocks
             def_wg = N <= 12 ? 8 : (N <= 13 ? 4 : 2);
         }
         a.threads = c->threads > 0 ? c->threads : def_threads;
-        // ping-pong + parents pays at 16 cities (the two live middle layers of
-        // all 256 resident blocks then stay in the Infinity Cache), not below
-        // (with a full wave of blocks: one block alone is latency-bound and the
-        // argmin's extra VALU only costs there)
-        // a full wave of blocks: the sub-cube kernels — variant 6 (hk_sub.h)
-        // where it has a configuration, else variant 5 (hk_tiled.h) — at
-        // 13-16 cities f64 and 16 cities i32 (round 2, per 16384 blocks:
-        // variant 5 n = 16 f64 7.6 vs 12.0 ms for variant 4, n = 15 3.75 vs
-        // 4.59, n = 14 1.80 vs 2.20, n = 13 0.88 vs 1.06, n = 16 i32 5.72 vs
-        // 7.63 for variant 2, profiles/r02/k1_tiled_v17_cfgs.log); the compact
-        // layer pass (variant 2) elsewhere
+        // a full wave of blocks: the sub-cube kernel, variant 6 (hk_sub.h), at
+        // 13-16 cities f64 and 16 cities i32, the compact layer pass (variant
+        // 2) elsewhere (measurements per size: DESIGN.md §4.0, §4.0a)
         const bool tiled = vbytes == 8 ? (N >= 12 && N <= 15) : N == 15;
         a.variant = c->variant >= 0 ? c->variant : (tiled && nblocks >= c->cu_count ? 6 : 2);
         if (a.variant == 6) {
             if (const SubCfg *cfg = pick_sub(c, N, vbytes))
                 return solve_sub(c, cfg, d_dist, n, nblocks, d_cost, d_tour, stream);
-            a.variant = 5;  // no variant-6 configuration for this size
         }
-        if (a.variant == 5) {
-            if (const TiledCfg *cfg = pick_tiled(c, N, vbytes))
-                return solve_tiled(c, cfg, d_dist, n, nblocks, d_cost, d_tour, stream);
-            a.variant = vbytes == 8 && N == 15 ? 4 : 2;  // no tiled configuration for this size
-        }
+        // no variant-6 configuration for this size (or K1=5, the retired
+        // variant 5, kept as an alias of this fall-back): ping-pong + parents
+        // pays at 16 cities f64 (the two live middle layers of all resident
+        // blocks then stay in the Infinity Cache), not below
+        if (a.variant >= 5) a.variant = vbytes == 8 && N == 15 ? 4 : 2;
         // variant 4 at 16 cities: one 512-thread workgroup per CU at 2 waves/SIMD
         // (256 VGPRs; heldkarp_impl.h TSPGPU_K1_WAVES_512V4) beats 1024 threads at 4
         if (c->threads <= 0 && a.variant == 4 && N == 15 && vbytes == 8) a.threads = 512;
         if (a.use_lds) {
             // as many resident workgroups as the LDS allows, then persistent
-            const int per_cu = (int)(160 * 1024 / lds_bytes_for(N, true, threads_for(N, true, 0), vbytes == 4 || a.variant >= 1, vbytes));
+            const int per_cu = (int)(160 * 1024 / lds_bytes_for(N, true, threads_for(N, true, 0), vbytes));
             const int cap = c->cu_count * (per_cu > 0 ? per_cu : 1);
             grid = nblocks < cap ? nblocks : cap;
         } else {
@@ -650,8 +584,9 @@ int tspgpu_ctx_create(const tspgpu_opts *opts, tspgpu_ctx **out)
     if (tspgpu::tuned("THREADS", &kv)) c->threads = (int)kv;
     if (tspgpu::tuned("LDS_TABLE_MAX_N", &kv)) c->lds_table_max_n = (int)kv < kLdsTableMaxN ? (int)kv : kLdsTableMaxN;
     if (tspgpu::tuned("K1", &kv)) {
+        // below 4: the compact layer pass (2); 4, 5 as given; above: 6
         const int v = (int)kv;
-        c->variant = v < 0 ? 1 : (v >= 6 ? 6 : (v >= 4 ? v : (v > 2 ? 2 : v)));
+        c->variant = v >= 6 ? 6 : (v >= 4 ? v : 2);
     }
     if (tspgpu::tuned("TILED_CFG", &kv)) c->tiled_cfg = (int)kv;
     if (tspgpu::tuned("WG_PER_CU", &kv)) c->wg_per_cu = kv > 0 ? (int)kv : 0;

@@ -356,15 +356,15 @@ class Context:
         return lib().tspgpu_last_grid(self.handle)
 
     def last_variant(self) -> int:
-        """K1 variant of the last batched launch (6: hk_sub_kernel, 5: hk_tiled_kernel, else heldkarp_kernel)."""
+        """K1 variant of the last batched launch (6: hk_sub_kernel; 4, 2: heldkarp_kernel; 0: n = 2)."""
         return lib().tspgpu_last_variant(self.handle)
 
     def k1_split_timing(self, enable: bool = True):
-        """Record an event between variant 5's forward and backtracking kernels."""
+        """Record an event between variant 6's forward and backtracking kernels."""
         self._check(lib().tspgpu_k1_split_timing(self.handle, int(enable)), "tspgpu_k1_split_timing")
 
     def k1_last_split_ms(self):
-        """(forward_ms, backtrack_ms) of the last variant-5 launch (waits for it)."""
+        """(forward_ms, backtrack_ms) of the last variant-6 launch (waits for it)."""
         f, b = ctypes.c_float(), ctypes.c_float()
         self._check(lib().tspgpu_k1_last_split_ms(self.handle, ctypes.byref(f), ctypes.byref(b)),
                     "tspgpu_k1_last_split_ms")
