@@ -12,7 +12,8 @@
  *
  * Return codes: 0 on success, otherwise a negative errno value
  *   -EINVAL  bad argument (n outside [2, TSPGPU_MAX_CITIES] (strict: 16), nblocks < 0,
- *            NULL pointer, non-finite or negative distance)
+ *            NULL pointer, non-finite or negative distance; -0.0 counts as
+ *            negative: a minimum over zeros of both signs has no defined sign)
  *   -ERANGE  n * max(d) >= INT_MAX: the reference's INT_MAX sentinel
  *            (tsp.cpp:411,453) would leave its tour undefined
  *   -ENODEV  no HIP device / device ordinal out of range
@@ -49,7 +50,10 @@ typedef struct
 {
     int device;      /* HIP device ordinal; -1 = the calling thread's current device */
     int strict;      /* 1: accept n <= 16 only (the reference's cap, tsp.cpp:289) */
-    int slots;       /* resident DP workspaces (persistent grid size); 0 = auto */
+    int slots;       /* resident DP workspaces = persistent grid size of the global-table
+                        layer kernels (11 cities and more); 0 = auto.  The LDS-table
+                        kernels (up to 10 cities) keep no workspace and the large-batch
+                        sub-cube kernel sizes its own grid: both ignore it. */
     int reserved[5]; /* must be zero */
 } tspgpu_opts;
 
@@ -377,7 +381,7 @@ int tspgpu_reduce(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double
  * answer.  Process-wide, read where each is used (K1 knobs at context
  * creation, K2 knobs at search creation).  The library reads no environment
  * variable of its own: the documented TSP_* variables belong to bin/tsp.
- * Names: K1, TILED_CFG, WG_PER_CU, THREADS, LDS_TABLE_MAX_N, WIDE_PULL,
+ * Names: K1, TILED_CFG, K1_CHUNK, WG_PER_CU, THREADS, LDS_TABLE_MAX_N, WIDE_PULL,
  * SEARCH_{KERNEL, HUNGRY, MIN_SPLIT, WALL_S, RING_LOG2, REFILL, TAIL, SUFFIX,
  * TWO_EDGE, CHAIN, LAGRANGE, MST, MST_MINREM, TAIL_CAP_LOG2, EXPAND_LOG2,
  * BUDGET, TIE, PAGEABLE, TAILS, CHAIN_CAP_LOG2, CHAIN_POISON, DEBUG, DEPTH,

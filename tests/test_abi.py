@@ -82,6 +82,26 @@ def test_validation_host_side():
     assert tspgpu.validate(np.zeros((1, 21, 21)), strict=False) == -errno.EINVAL
 
 
+def test_validation_refuses_negative_zero():
+    """-0.0 passes `v >= 0.0`, but a minimum over zeros of both signs has no
+    sign the kernels (v_min_f64) and the reference (strict <) agree on: it is
+    refused like any negative distance; +0.0 in the same places is accepted."""
+    for n in (5, 13, 16):
+        part = np.zeros((1, n, n))
+        part[0, 0, 1] = part[0, 1, 2] = -0.0
+        cycle = np.zeros((1, n, n))
+        for i in range(n):
+            cycle[0, i, (i + 1) % n] = -0.0  # (measured: the kernels return -0.0 here, the oracle +0.0)
+        for bad in (part, np.full((1, n, n), -0.0), cycle):
+            assert np.signbit(bad).any()
+            assert tspgpu.validate(bad) == -errno.EINVAL
+            assert tspgpu.validate(np.abs(bad)) == 0
+        ok = np.ones((3, n, n))
+        assert tspgpu.validate(ok) == 0
+        ok[2, n - 1, 0] = -0.0
+        assert tspgpu.validate(ok) == -errno.EINVAL
+
+
 def test_validation_i32_host_side():
     ok = np.zeros((2, 5, 5), dtype=np.int32)
     assert tspgpu.validate_i32(ok) == 0

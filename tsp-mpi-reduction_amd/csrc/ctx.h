@@ -36,6 +36,7 @@ struct tspgpu_ctx {
                          // 4 = 2 + ping-pong values + parent words,
                          // 2 = compact layer pass + next-row prefetch
     int tiled_cfg = -1;  // K1 variant 6 configuration id (k1_cfg.h); -1 = per-(n, type) default
+    int k1_chunk = 65536;  // most blocks per variant-6 chunk (ensure_slots; knob K1_CHUNK for tests)
     void *d_tinfo[16] = {};        // TiledInfo per L (variant 6)
     void *d_subrows[16] = {};      // SubRow table per L (variant 6)
     char *d_tslots = nullptr;      // variant 6 slots (one per block of a launch)

@@ -18,6 +18,7 @@
 
 #include <cerrno>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -323,7 +324,7 @@ int tspgpu_solve_instance(tspgpu_ctx *c, const double *dist, int n, double *cost
         // tspgpu_validate caps n at 20: check the values here
         double mx = 0.0;
         for (int i = 0; i < n * n; ++i) {
-            if (!(dist[i] >= 0.0) || !(dist[i] < INFINITY)) return -EINVAL;
+            if (!(dist[i] >= 0.0) || std::signbit(dist[i]) || !(dist[i] < INFINITY)) return -EINVAL;
             mx = dist[i] > mx ? dist[i] : mx;
         }
         rc = (double)n * mx >= (double)INT_MAX ? -ERANGE : 0;

@@ -187,9 +187,11 @@ int ensure_tiled_info(tspgpu_ctx *c, int L)
 // at that moment (other contexts or ranks on the same GPU keep theirs),
 // halved while the allocation fails, down to 64 blocks.  A slot area far
 // larger than a later launch needs (> 4x and > 8 GB) is given back first.
+// (The knob K1_CHUNK lowers the 65536 so that tests can run several chunks
+// from a small batch.)
 int ensure_slots(tspgpu_ctx *c, int nblocks, size_t slot, int *chunk)
 {
-    int ch = std::min(nblocks, 65536);
+    int ch = std::min(nblocks, c->k1_chunk);
     const size_t need = (size_t)ch * slot;
     if (c->d_tslots && c->tslots_bytes > 4 * need && c->tslots_bytes > ((size_t)8 << 30)) {
         (void)hipFree(c->d_tslots);
@@ -538,7 +540,10 @@ int tspgpu_validate(const double *dist, int n, int nblocks, int strict)
         double mx = 0.0;
         for (int i = 0; i < n * n; ++i) {
             const double v = d[i];
-            if (!(v >= 0.0) || !std::isfinite(v)) return -EINVAL;
+            // (-0.0 passes v >= 0.0: the kernels' v_min_f64 orders it below +0.0
+            // where the reference's strict < keeps the first, so the sign of a
+            // zero cost could differ from the reference's — refused)
+            if (!(v >= 0.0) || std::signbit(v) || !std::isfinite(v)) return -EINVAL;
             if (v > mx) mx = v;
         }
         // Every partial tour has at most n edges: below INT_MAX the reference's
@@ -589,6 +594,7 @@ int tspgpu_ctx_create(const tspgpu_opts *opts, tspgpu_ctx **out)
         c->variant = v >= 6 ? 6 : (v >= 4 ? v : 2);
     }
     if (tspgpu::tuned("TILED_CFG", &kv)) c->tiled_cfg = (int)kv;
+    if (tspgpu::tuned("K1_CHUNK", &kv) && kv >= 1.0) c->k1_chunk = kv < 65536.0 ? (int)kv : 65536;
     if (tspgpu::tuned("WG_PER_CU", &kv)) c->wg_per_cu = kv > 0 ? (int)kv : 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
