@@ -259,7 +259,10 @@ int tspgpu_search_solve(tspgpu_ctx *ctx, const void *dist, int dtype, int n, dou
  * the (n-1)! tours is folded (the left fold of tsp.cpp), the tours within the
  * incumbent are recorded and the DP's tie rule picks among the optimal ones,
  * so the result equals tspgpu_search_solve / tsp().  stats->nodes counts every
- * partial path (about e*(n-1)!).  Practical up to ~15 cities. */
+ * partial path (about e*(n-1)!).  Practical up to ~16 cities on one GPU; this
+ * one-shot is one shard on the context's GPU — to enumerate one instance over
+ * several GPUs or ranks, create the shards with TSPGPU_SEARCH_EXHAUSTIVE
+ * (below; bin/tsp_search --solver enum --gpus G, search_dist.solve_sharded). */
 int tspgpu_search_enumerate(tspgpu_ctx *ctx, const void *dist, int dtype, int n, double *cost_out,
                             int32_t *tour_out, tspgpu_search_stats *stats);
 
@@ -281,6 +284,40 @@ int tspgpu_search_create(tspgpu_ctx *ctx, const void *dist, int dtype, int n, in
  * direction; every shard of an instance gets the same bound), so a driver
  * needs no host heuristic and no tspgpu_search_set_bound before the search. */
 #define TSPGPU_SEARCH_DEVICE_BOUND 1
+/* TSPGPU_SEARCH_EXHAUSTIVE: this search is shard `shard` of `nshards` of the
+ * exhaustive enumeration (tspgpu_search_enumerate's settings: no bound test,
+ * the long round budget, knobs ENUM_KERNEL and SEARCH_RECORD_CAP).  Every
+ * shard count gives the same bit-exact cost and tie-broken tour as tsp().
+ *  - Shard rule.  For 7 <= n <= 16 the shard is ONE launch of the enumeration
+ *    kernel: its work items are the (n-1)!/6! prefixes of depth n-7
+ *    (tspgpu_search_info: depth, items), of which shard s folds p = i*S + s,
+ *    i < local_items = items/S + (items % S > s) — the static interleave of
+ *    the branch-and-bound seeds.  Other n (or knob ENUM_KERNEL=0) run the round
+ *    kernels with the bound off over this shard's seeds.
+ *  - Empty shards.  S may exceed the prefix count (n = 7 has one prefix, n = 8
+ *    seven): a shard with local_items == 0 launches nothing, folds no tour,
+ *    keeps its incumbent at the bound and reports no tie slot (found = 0).
+ *  - The bound.  tspgpu_search_set_bound before the run, with the left-fold
+ *    cost of a real tour, the same on every shard (tspgpu_heuristic_tour):
+ *    tours within it are recorded, so a loose bound only costs records.
+ *    TSPGPU_SEARCH_DEVICE_BOUND | TSPGPU_SEARCH_EXHAUSTIVE is not supported
+ *    (-EINVAL).
+ *  - tspgpu_search_run_all runs the shard (synchronous).  tspgpu_search_chain
+ *    on an enumeration-kernel shard enqueues the one launch and the readbacks
+ *    (counters, the shard's tie slot at its incumbent, first records) with one
+ *    synchronisation, sets *done = 1 and calls the hook ZERO times: there are
+ *    no levels, and no pruning an exchanged incumbent could help; the count
+ *    is the same on every shard.  On the round kernels it returns *done = 0
+ *    like any search that is not a chain: continue with start / step.
+ *  - The winner over the shards is the branch-and-bound's: MIN of the
+ *    incumbents, then MIN of the tie keys of the shards that hold a tour of
+ *    that cost (tspgpu_search_tie_slot), else the records.
+ *  - nodes (tspgpu_search_counters) counts every partial path: cumulative over
+ *    the runs of a search (a second run_all with the optimum as the bound, the
+ *    records fallback, adds its own), and the partial paths above the work
+ *    items are counted by shard 0 alone, so the sum over the shards of one
+ *    instance is exactly the one-shard count. */
+#define TSPGPU_SEARCH_EXHAUSTIVE 2
 int tspgpu_search_create_ex(tspgpu_ctx *ctx, const void *dist, int dtype, int n, int shard, int nshards, int depth,
                             int flags, tspgpu_search **out);
 int tspgpu_search_destroy(tspgpu_search *s);

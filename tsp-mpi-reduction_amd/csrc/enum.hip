@@ -24,7 +24,11 @@
 //     rolled loops and records every tour within the incumbent (atomicMin on
 //     the 64-bit cost word, then a record slot), like search.hip.
 // No bound, no queue, no rounds: the enumeration is uniform, a grid-stride
-// loop over the prefixes balances it.
+// loop over the prefixes balances it.  Over S GPUs (or ranks) shard s folds
+// the prefixes p = i*S + s — the interleave of the branch-and-bound seeds —
+// so every shard gets items/S prefixes (+1 for the first items % S shards), a
+// shard beyond the prefix count none; the winner over the shards is the MIN of
+// the incumbents, then of the device tie keys (search_abi.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -82,7 +86,11 @@ __device__ __forceinline__ void complete(const V (&s)[TL][TL], const V (&d0)[TL]
     }
 }
 
-template <typename V, int NN>
+// SH (several shards, a.nshards > 1): this shard folds the prefixes
+// p = i * nshards + shard, i < local — the static interleave of seed_body —
+// and the grid-stride loop runs over i.  One shard keeps the plain index (no
+// multiply-add in its loop): SH = false is the kernel as it was.
+template <typename V, int NN, bool SH>
 __global__ __launch_bounds__(256) void enum_kernel(SearchArgs a)
 {
     constexpr int N = NN - 1;  // inner cities 1..N
@@ -96,9 +104,15 @@ __global__ __launch_bounds__(256) void enum_kernel(SearchArgs a)
     unsigned long long lanes = 0;  // wave-uniform
     TieCache tcache;
     const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t base = blockIdx.x * blockDim.x; base < a.items; base += stride) {
-        const uint32_t idx = base + threadIdx.x;
-        const bool act = idx < a.items;
+    // prefixes of this shard (a.items stays the global count)
+    const uint32_t local = SH ? a.items / a.nshards + (a.items % a.nshards > a.shard ? 1u : 0u) : a.items;
+    for (uint32_t base = blockIdx.x * blockDim.x; base < local; base += stride) {
+        const uint32_t li = base + threadIdx.x;
+        const bool act = li < local;
+        // li < local means li * nshards + shard < a.items, and a.items <= 15!/6!
+        // = 1,816,214,400 < 2^32 (NN <= 16): the global index fits 32 bits; a
+        // lane beyond the shard's count never forms it
+        const uint32_t idx = SH ? (act ? li * a.nshards + a.shard : 0u) : li;
         lanes += (unsigned long long)__popcll(__ballot(act));
         // ---- decode the prefix: digit l picks the dig[l]-th unused city
         int dig[G > 0 ? G : 1];
@@ -198,13 +212,20 @@ __global__ __launch_bounds__(256) void enum_kernel(SearchArgs a)
             }
         }
     }
-    if (__lane_id() == 0) atomicAdd(stat_line(a), lanes * (unsigned long long)kTailNodes);
+    // (the first wave of the launch also adds the partial paths of the prefix
+    // levels, counted by the host: a.enum_upper, zero on every shard but 0)
+    if (__lane_id() == 0)
+        atomicAdd(stat_line(a), lanes * (unsigned long long)kTailNodes +
+                                    (blockIdx.x == 0 && threadIdx.x == 0 ? a.enum_upper : 0ull));
 }
 
 template <typename V, int NN>
 hipError_t launch_n(const SearchArgs &a, int grid)
 {
-    hipLaunchKernelGGL((enum_kernel<V, NN>), dim3(grid), dim3(256), 0, a.stream, a);
+    if (a.nshards > 1)
+        hipLaunchKernelGGL((enum_kernel<V, NN, true>), dim3(grid), dim3(256), 0, a.stream, a);
+    else
+        hipLaunchKernelGGL((enum_kernel<V, NN, false>), dim3(grid), dim3(256), 0, a.stream, a);
     return hipGetLastError();
 }
 

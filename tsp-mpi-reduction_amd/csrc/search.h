@@ -153,6 +153,11 @@ struct SearchArgs {
     // the chain is timed without events (an event costs ~5 us of the GPU's
     // timeline between two launches); null: not stored
     unsigned long long *t_start;
+    // enum_kernel: the partial paths of the prefix levels above its lanes
+    // (sum of N!/(N-l)!, l = 1..N-6; host-computed), added to the node
+    // statistic once per launch — by shard 0 only, so the shards' nodes sum to
+    // the one-shard count
+    unsigned long long enum_upper;
     hipStream_t stream;
 };
 
@@ -265,7 +270,9 @@ __device__ __forceinline__ unsigned long long *stat_line(const SearchArgs &a)
 size_t search_lds_bytes(int n, bool f64, int kernel = 2);
 hipError_t launch_seed(const SearchArgs &a, bool f64, int grid);
 hipError_t launch_round(const SearchArgs &a, bool f64, int grid);
-// exhaustive enumeration (enum.hip), 7 <= n <= 16: a.items = depth-(n-7) prefixes
+// exhaustive enumeration (enum.hip), 7 <= n <= 16: a.items = depth-(n-7)
+// prefixes (the global count), of which shard a.shard of a.nshards folds
+// p = i * nshards + shard; the grid is sized for the shard's count
 hipError_t launch_enum(const SearchArgs &a, bool f64, int grid);
 // frontier search (enum.hip): one level of a.in -> a.out / a.tail_out, and
 // the register tails of a.tail_out (a.tail_len in {5, 6})

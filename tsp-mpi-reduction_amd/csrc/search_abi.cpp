@@ -321,8 +321,11 @@ extern "C" {
 // (bound: the initial incumbent, written with the counter words; null: none)
 // (dev_bound: the init launch computes the bound on the device, search.hip
 // init_heuristic; s->dev_heur says whether it did)
+// (enum_shard: an exhaustive shard that will run on the enumeration kernel —
+// it has no frontier, so none of the frontier's buffers is allocated)
+static bool use_enum_kernel(int n) { return n >= 7 && n <= 16 && tuned_or("ENUM_KERNEL", 1) != 0; }
 static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int shard, int nshards, int depth,
-                         const double *bound, tspgpu_search **out, bool dev_bound = false)
+                         const double *bound, tspgpu_search **out, bool dev_bound = false, bool enum_shard = false)
 {
     if (!c || !out) return -EINVAL;
     *out = nullptr;
@@ -381,7 +384,7 @@ static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int 
     if (depth > N - 1) depth = N - 1;
     while (depth > 1 && falling(N, depth) >= (1ull << 31)) --depth;
     if (tuned("SEARCH_BUDGET", &kv) && kv > 0) s->budget = (uint32_t)kv;
-    s->frontier = s->tail_len && s->kernel == 2 && N - s->tail_len > depth;
+    s->frontier = s->tail_len && s->kernel == 2 && N - s->tail_len > depth && !enum_shard;
     // the frontier search expands level by level with its own bounds: a
     // smaller seed set (~64 prefixes per CU) costs less than the round
     // kernels' one-per-lane (measured at n = 16: depth 4 vs 5, 0.14 vs 0.16 ms)
@@ -651,11 +654,45 @@ int tspgpu_search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int 
     return search_create(c, dist, dtype, n, shard, nshards, depth, nullptr, out);
 }
 
+// The settings a fresh search takes after create — the one place both the
+// one-shots (tspgpu_search_solve / tspgpu_search_enumerate) and
+// TSPGPU_SEARCH_EXHAUSTIVE go through, so they cannot drift apart.
+static void set_mode(tspgpu_search *s, bool exhaustive)
+{
+    const int n = s->n;
+    s->noprune = exhaustive ? 1 : 0;
+    // enumeration work is uniform and every lane reaches the register tails:
+    // long budgets (fewer, fuller rounds) win (profiles/r01/k2_exhaustive_budget.log)
+    if (exhaustive && !tuned("SEARCH_BUDGET", nullptr)) s->budget = 16384;
+    // 7 <= n <= 16: the register-tail enumeration kernel (enum.hip), any shard
+    // count; knob ENUM_KERNEL=0 keeps the round kernels (tests compare both)
+    s->enum_kernel = exhaustive && use_enum_kernel(n);
+    if (double v; tuned("SEARCH_RECORD_CAP", &v) && v > 0)  // tests: force the second phase
+        s->rec_cap = (unsigned int)std::min<double>(v, s->rec_cap);
+    if (s->enum_kernel) {
+        // its work items are the depth-(N-6) prefixes, split over the shards like
+        // the seeds (tspgpu_search_info reports them); no seeds, no frontier
+        const int N = n - 1, G = N - 6;
+        s->depth = G;
+        s->items = falling(N, G);  // <= 15!/6! < 2^31
+        s->local_items = s->items / s->nshards + (s->items % s->nshards > (uint64_t)s->shard ? 1 : 0);
+        s->frontier = false;
+    }
+}
+
 int tspgpu_search_create_ex(tspgpu_ctx *c, const void *dist, int dtype, int n, int shard, int nshards, int depth,
                             int flags, tspgpu_search **out)
 {
-    if (flags & ~TSPGPU_SEARCH_DEVICE_BOUND) return -EINVAL;
+    if (flags & ~(TSPGPU_SEARCH_DEVICE_BOUND | TSPGPU_SEARCH_EXHAUSTIVE)) return -EINVAL;
     const bool dev = (flags & TSPGPU_SEARCH_DEVICE_BOUND) != 0;
+    if (flags & TSPGPU_SEARCH_EXHAUSTIVE) {
+        // (no device bound here: the enumeration's initial incumbent comes from
+        // tspgpu_search_set_bound, the host heuristic the one-shot uses)
+        if (dev) return -EINVAL;
+        int rc = search_create(c, dist, dtype, n, shard, nshards, depth, nullptr, out, false, use_enum_kernel(n));
+        if (!rc) set_mode(*out, true);
+        return rc;
+    }
     int rc = search_create(c, dist, dtype, n, shard, nshards, depth, nullptr, out, dev);
     if (rc || !dev || (*out)->dev_heur) return rc;
     // (pageable staging knob: no create launch, so the host's bound)
@@ -933,7 +970,14 @@ static int build_suffix(tspgpu_search *s, bool launch, uint32_t *sets_out)
 }
 
 static int search_start(tspgpu_search *s, bool sync);
-int tspgpu_search_start(tspgpu_search *s) { return s ? search_start(s, true) : -EINVAL; }
+static int run_enum(tspgpu_search *s, bool fetch);
+int tspgpu_search_start(tspgpu_search *s)
+{
+    if (!s) return -EINVAL;
+    // (an enum-kernel shard has no seeds and no rounds: start is its one launch, nothing is pending after it)
+    if (s->noprune && s->enum_kernel) return run_enum(s, false);
+    return search_start(s, true);
+}
 
 // sync = false (chained searches): the seeds' launch is only enqueued, their
 // count stays on the device (word 4), s->pending is the upper bound
@@ -1489,42 +1533,49 @@ static int run_persist(tspgpu_search *s)
 }
 
 // Exhaustive enumeration in ONE launch (enum.hip): a lane per depth-(N-6)
-// prefix, its 720 completions in registers.  nodes = the prefix levels (host,
-// exact) + 1,956 per lane (device).
-static int run_enum(tspgpu_search *s)
+// prefix of this shard (p = i * nshards + shard), its 720 completions in
+// registers.  nodes = the prefix levels (host, exact; counted by shard 0, so
+// the shards' nodes sum to the one-shard count) + 1,956 per lane (device),
+// added to the statistics by the launch: cumulative over the runs of a search
+// (the sharded drivers' second phase relies on that, as for the round kernels).
+// A shard without a prefix (nshards > the prefix count) launches nothing.
+// fetch: the chained form's readbacks ride on the one synchronisation.
+static int run_enum(tspgpu_search *s, bool fetch)
 {
     (void)hipSetDevice(s->ctx->device);
     hipStream_t st = s->ctx->stream;
+    s->fresh = false;
+    s->fetched = false;
     const int N = s->n - 1, G = N - 6;
-    unsigned long long upper = 0;
-    for (int l = 1; l <= G; ++l) upper += falling(N, l);
-    SearchArgs a = args_of(s);
-    a.depth = G;
-    a.items = (uint32_t)falling(N, G);
-    const uint64_t blocks = (a.items + kSearchThreads - 1) / kSearchThreads;
+    SearchArgs a = args_of(s);  // (depth, items and local_items are the enumeration's: set_mode)
+    if (s->shard == 0)
+        for (int l = 1; l <= G; ++l) a.enum_upper += falling(N, l);
+    const uint64_t blocks = (s->local_items + kSearchThreads - 1) / kSearchThreads;
     int per_cu = 8;
     per_cu = std::max(1, tuned_int("ENUM_WG_PER_CU", per_cu));
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)s->ctx->cu_count * per_cu));
-    hipError_t e = hipMemcpyAsync(s->d_stats, &upper, 8, hipMemcpyHostToDevice, st);  // line 0, nodes
-    if (e != hipSuccess) return herr(e);
-    (void)hipEventRecord(s->e0, st);
-    e = launch_enum(a, s->dtype == TSPGPU_F64, grid);
-    (void)hipEventRecord(s->e1, st);
+    const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)s->ctx->cu_count * per_cu);
+    hipError_t e = hipSuccess;
+    if (grid > 0) {
+        (void)hipEventRecord(s->e0, st);
+        e = launch_enum(a, s->dtype == TSPGPU_F64, grid);
+        (void)hipEventRecord(s->e1, st);
+    }
+    fetch = fetch && s->h_stage;
+    if (e == hipSuccess && fetch) e = enqueue_fetch(s);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return herr(e);
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
-    s->depth = G;
-    s->items = a.items;
+    if (grid > 0 && hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
     s->pending = 0;
     ++s->rounds;
+    s->fetched = fetch;
     return 0;
 }
 
 int tspgpu_search_run_all(tspgpu_search *s)
 {
     if (!s) return -EINVAL;
-    if (s->noprune && s->enum_kernel) return run_enum(s);
+    if (s->noprune && s->enum_kernel) return run_enum(s, false);
     if (s->kernel == 3 && !s->noprune) return run_persist(s);
     s->fresh = false;
     if (s->nshards == 1 && chainable(s)) {
@@ -1550,6 +1601,16 @@ int tspgpu_search_chain(tspgpu_search *s, int exchange_every, tspgpu_level_hook 
     *done = 0;
     (void)hipSetDevice(s->ctx->device);
     s->fresh = false;
+    if (s->noprune && s->enum_kernel) {
+        // an exhaustive shard on the enum kernel: its one launch and the fetch,
+        // one synchronisation; no levels and no pruning an exchanged incumbent
+        // could help, so the hook is never called (on any shard: they pair up)
+        const int rc = run_enum(s, true);
+        if (rc) return rc;
+        *done = 1;
+        s->fresh = s->fetched;
+        return 0;
+    }
     if (!chainable(s)) {
         // the same number of exchanges as a chained shard would enqueue
         const int levels = s->frontier ? s->n - 1 - s->tail_len - s->depth : 0;
@@ -1728,19 +1789,11 @@ static int search_solve(tspgpu_ctx *c, const void *dist, int dtype, int n, doubl
                            dev_bound);
     if (threaded) ht.join();
     if (rc) return rc;
-    s->noprune = noprune;
     if (dev_bound && !s->dev_heur) {  // (pageable staging: no init launch, the host's bound)
         hrc = tspgpu_heuristic_tour(dist, dtype, n, &ub, nullptr);
         if (!hrc) hrc = tspgpu_search_set_bound(s, ub);
     }
-    // enumeration work is uniform and every lane reaches the register tails:
-    // long budgets (fewer, fuller rounds) win (profiles/r01/k2_exhaustive_budget.log)
-    if (noprune && !tuned("SEARCH_BUDGET", nullptr)) s->budget = 16384;
-    // 7 <= n <= 16, one shard: the register-tail enumeration kernel (enum.hip);
-    // knob ENUM_KERNEL=0 keeps the round kernels (tests compare both)
-    s->enum_kernel = noprune && n >= 7 && n <= 16 && tuned_or("ENUM_KERNEL", 1) != 0;
-    if (double v; tuned("SEARCH_RECORD_CAP", &v) && v > 0)  // tests: force the second phase
-        s->rec_cap = (unsigned int)std::min<double>(v, s->rec_cap);
+    set_mode(s, noprune != 0);
     rc = hrc;
     if (dbg) T1 = clk::now();
     if (!rc && threaded) rc = tspgpu_search_set_bound(s, ub);

@@ -14,7 +14,8 @@
 //                                                         tests/golden/tsplib/gr17.tsp
 //   options: --gpus G (shard g on device g mod visible devices)  --rccl (the RCCL
 //            exchange even for G = 1)  --solver auto|wide|k1|k2|enum  --verify (n <= 20: K1 too)
-//   (enum: every tour enumerated on one GPU, BASELINE config 2)
+//   (enum: every tour enumerated, BASELINE config 2; with --gpus G >= 2 over G
+//   shards, shard g folding the prefixes p = i*G + g: TSPGPU_SEARCH_EXHAUSTIVE)
 //   auto = K1-wide (the DP with every CU on each layer) up to 25 cities on one
 //   GPU, else K2 over the GPUs.
 //
@@ -28,7 +29,9 @@
 // combined in place with an RCCL all-reduce MIN (uint64, over xGMI; through
 // the host when shards share a device), and the final optimum is that
 // all-reduce's result; the optimal records of all shards then go through
-// tspgpu_select_tour.
+// tspgpu_select_tour.  --solver enum --gpus G runs the same driver over
+// exhaustive shards (one enumeration launch each, no in-chain exchange) and
+// prints the tours folded, the rate and the shards' kernel times.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -273,6 +276,7 @@ struct Result {
     const char *exchange = "none";  // how the shards' incumbents were combined (K2)
     int tie = 0;      // K2 over shards: the winner came from the device tie keys (no record read)
     int chained = 0;  // K2 over shards: every shard ran as one device chain
+    double shard_ms_min = 0.0, shard_ms_max = 0.0;  // kernel time of the fastest / slowest shard
 };
 
 // K2 over G shards of this process, shard g on device g mod (visible
@@ -290,6 +294,9 @@ struct Result {
 // that w0) picks the least key, certified once (tspgpu_tie_tour).  Only when
 // that certificate cannot be given are the optimal records read and passed
 // to tspgpu_select_tour.
+// exhaustive: the shards are created with TSPGPU_SEARCH_EXHAUSTIVE (shard g
+// of the enumeration: one launch per shard for 7 <= n <= 16, its chain calls
+// the hook zero times on every shard); the exchanges and the winner are the same.
 constexpr int kChainExchangeLevels = 2;
 
 struct ChainHook {
@@ -303,7 +310,7 @@ void chain_exchange(void *user, void *stream, void *word)
     if (ncclAllReduce(word, word, 1, ncclUint64, ncclMin, h->comm, (hipStream_t)stream) != ncclSuccess) h->rc = -EIO;
 }
 
-int search_multi(const Instance &in, int G, bool force_rccl, int exchange_every, Result &res)
+int search_multi(const Instance &in, int G, bool force_rccl, int exchange_every, bool exhaustive, Result &res)
 {
     int ndev = tspgpu_device_count();
     if (ndev < 1) ndev = 1;
@@ -342,7 +349,10 @@ int search_multi(const Instance &in, int G, bool force_rccl, int exchange_every,
             tspgpu_ctx *ctx = nullptr;
             tspgpu_search *s = nullptr;
             int rc = tspgpu_ctx_create(&o, &ctx);
-            if (!rc) rc = tspgpu_search_create(ctx, dist_ptr(in), in.dtype, in.n, g, G, 0, &s);
+            if (!rc)
+                rc = exhaustive ? tspgpu_search_create_ex(ctx, dist_ptr(in), in.dtype, in.n, g, G, 0,
+                                                          TSPGPU_SEARCH_EXHAUSTIVE, &s)
+                                : tspgpu_search_create(ctx, dist_ptr(in), in.dtype, in.n, g, G, 0, &s);
             if (!rc) rc = tspgpu_search_set_bound(s, ub);
             hipStream_t st = ctx ? (hipStream_t)tspgpu_stream(ctx) : nullptr;
             // the key exchange's device words, allocated up front: a shard that
@@ -491,6 +501,8 @@ int search_multi(const Instance &in, int G, bool force_rccl, int exchange_every,
     for (int g = 0; g < G; ++g) {
         res.nodes += nodes[g];
         res.kernel_ms = std::max(res.kernel_ms, ms[g]);
+        res.shard_ms_min = g == 0 ? ms[g] : std::min(res.shard_ms_min, ms[g]);
+        res.shard_ms_max = std::max(res.shard_ms_max, ms[g]);
         res.rounds = std::max(res.rounds, rounds[g]);
     }
     return 0;
@@ -573,7 +585,8 @@ int main(int argc, char **argv)
         else if (a == "--dump-matrix") dump = true;  // print the instance's matrix and exit (no GPU)
         else {
             std::fprintf(stderr, "usage: tsp_search (--random N [--seed S] [--clustered K] | --cities FILE "
-                                 "[--tsplib-round] | --matrix FILE | --tsplib FILE) [--gpus G] [--rccl] [--exchange-every S] [--solver auto|wide|k1|k2|enum] [--verify]\n");
+                                 "[--tsplib-round] | --matrix FILE | --tsplib FILE) [--gpus G] [--rccl] [--exchange-every S] [--solver auto|wide|k1|k2|enum] [--verify]\n"
+                                 "  --solver enum --gpus G: the exhaustive enumeration over G shards (G >= 2; one GPU otherwise)\n");
             return 1;
         }
     }
@@ -616,16 +629,21 @@ int main(int argc, char **argv)
         die("--solver must be auto, wide, k1, k2 or enum");
 
     Result res;
+    // the enumeration over G >= 2 shards goes through the sharded driver; one
+    // GPU keeps the one-shot (and its output)
+    bool enum_multi = solver == "enum" && gpus >= 2;
     const auto t0 = std::chrono::steady_clock::now();
     int rc = solver == "k1"     ? solve_k1(in, res)
              : solver == "wide" ? solve_wide(in, res)
-             : solver == "enum" ? solve_enum(in, res)
-                                : search_multi(in, gpus, force_rccl, exchange_every, res);
+             : solver == "enum" && !enum_multi
+                 ? solve_enum(in, res)
+                 : search_multi(in, gpus, force_rccl, exchange_every, enum_multi, res);
     if (rc == -EOVERFLOW && in.n <= TSPGPU_WIDE_MAX_CITIES) {
         // more tied optima than the record buffers hold (e.g. coincident cities):
         // the DP returns the same tour directly
         std::fprintf(stderr, "tsp_search: too many tied optimal tours to enumerate; answering with the DP\n");
         solver = "wide";
+        enum_multi = false;
         rc = solve_wide(in, res);
     }
     const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -634,7 +652,7 @@ int main(int argc, char **argv)
         return 3;
     }
     std::printf("cities %d  mode %s  solver %s  gpus %d\n", in.n, in.dtype == TSPGPU_F64 ? "f64" : "i32",
-                solver.c_str(), solver == "k2" ? gpus : 1);
+                solver.c_str(), solver == "k2" || enum_multi ? gpus : 1);
     std::printf("optimal cost %.17g (%f)\n", res.cost, res.cost);
     std::printf("tour");
     for (int t : res.tour) std::printf(" %d", t);
@@ -643,8 +661,16 @@ int main(int argc, char **argv)
         std::printf("search nodes %llu  rounds %d  kernel %.3f ms  %.3f Gnodes/s  wall %.3f ms  exchange %s\n",
                     (unsigned long long)res.nodes, res.rounds, res.kernel_ms,
                     res.kernel_ms > 0 ? res.nodes / res.kernel_ms / 1e6 : 0.0, wall, res.exchange);
-    if (solver == "k2" && std::strcmp(res.exchange, "none") != 0)  // (the sharded driver)
+    if ((solver == "k2" || enum_multi) && std::strcmp(res.exchange, "none") != 0)  // (the sharded driver)
         std::printf("winner %s  chained %d\n", res.tie ? "tie-key" : "records", res.chained);
+    if (enum_multi) {
+        // every tour once over the shards; the rate over the slowest shard's kernel time
+        long double tours = 1.0L;
+        for (int k = 2; k < in.n; ++k) tours *= k;
+        std::printf("tours %.0Lf  %.3f Gtours/s  shard kernel ms min/max %.3f/%.3f\n", tours,
+                    res.shard_ms_max > 0 ? (double)tours / res.shard_ms_max / 1e6 : 0.0, res.shard_ms_min,
+                    res.shard_ms_max);
+    }
     if (solver == "wide")
         std::printf("kernel %.3f ms  wall %.3f ms\n", res.kernel_ms, wall);
     else if (solver != "k2" && solver != "enum")

@@ -162,9 +162,17 @@ def _key_u64(v: int) -> int:
 
 
 def solve_sharded(ctx, dist, group=None, depth: int = 0, device=None, exchange_every: int | None = None,
-                  exchange_levels: int = 2, bound: str | None = None):
+                  exchange_levels: int = 2, bound: str | None = None, exhaustive: bool = False):
     """Search one instance over the ranks of `group` (None: the default group,
     or a single process when torch.distributed is not initialised).
+
+    exhaustive=True: the exhaustive enumeration instead of the branch and
+    bound, rank r folding the prefixes p = i*W + r (TSPGPU_SEARCH_EXHAUSTIVE;
+    for 7 <= n <= 16 each rank's shard is one launch, chained with ZERO
+    in-chain exchanges: no pruning they could help).  The bound is the host
+    heuristic's (the one-shot's; the same on every rank — bound="device" is
+    not available), the winner logic below is unchanged, and stats["nodes"] is
+    exactly the one-GPU enumeration's count.
 
     1. The initial bound.  bound="device" (the default): the search's create
        launch computes it on the GPU (nearest neighbour + 2-opt from spread
@@ -239,9 +247,11 @@ def solve_sharded(ctx, dist, group=None, depth: int = 0, device=None, exchange_e
     # cities r, r+W, ...; all-reduce MIN of the costs) and computed on a thread
     # while the search is created (ctypes releases the GIL); below, every rank
     # computes the same four-start bound itself (microseconds; no collective)
-    bound = bound or os.environ.get("TSPGPU_SHARDED_BOUND", "device")
+    bound = bound or ("host" if exhaustive else os.environ.get("TSPGPU_SHARDED_BOUND", "device"))
     if bound not in ("device", "host"):
         raise ValueError(f"bound must be 'device' or 'host', not {bound!r}")
+    if exhaustive and bound == "device":
+        raise ValueError("exhaustive=True takes the host bound (TSPGPU_SEARCH_EXHAUSTIVE has no device bound)")
     dev_bound = bound == "device"
     split = not dev_bound and collective and world > 1 and len(dist) >= 20
     heur = {}
@@ -260,8 +270,9 @@ def solve_sharded(ctx, dist, group=None, depth: int = 0, device=None, exchange_e
     th = threading.Thread(target=_heuristic) if not dev_bound and len(dist) >= 20 else None  # (smaller: no thread)
     if th is not None:
         th.start()
+    mode = {"exhaustive": True} if exhaustive else {}  # (only when set: stand-ins of Search need not know it)
     try:
-        S = tspgpu.Search(ctx, dist, shard=rank, nshards=world, depth=depth, device_bound=dev_bound)
+        S = tspgpu.Search(ctx, dist, shard=rank, nshards=world, depth=depth, device_bound=dev_bound, **mode)
     finally:
         if th is not None:
             th.join()
@@ -430,7 +441,7 @@ def solve_sharded(ctx, dist, group=None, depth: int = 0, device=None, exchange_e
                  "wall_s": wall, "tie": tie, "record_gather": gathered, "chained": int(chained),
                  "collectives": ncoll[0], "exchanges": exchanges, "hooks": hooks, "exchange_levels": exchange_levels,
                  "exchange_every": exchange_every, "world": world,
-                 "backend": backend, "host_phases_ms": ph, "bound": bound}
+                 "backend": backend, "host_phases_ms": ph, "bound": bound, "exhaustive": bool(exhaustive)}
         return cost, tour, stats
     finally:
         S.close()

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
 )
 
 F64, I32 = 0, 1
+SEARCH_DEVICE_BOUND, SEARCH_EXHAUSTIVE = 1, 2  # tspgpu_search_create_ex flags
 SEARCH_MAX_CITIES = 32
 MAX_CITIES = 20  # TSPGPU_MAX_CITIES: the batched K1 (extension sizes above the reference's 16)
 
@@ -644,14 +645,20 @@ class Search:
     """One instance (or shard `shard` of `nshards`) of the K2 search on a Context."""
 
     def __init__(self, ctx: "Context", dist, shard: int = 0, nshards: int = 1, depth: int = 0,
-                 device_bound: bool = False):
+                 device_bound: bool = False, exhaustive: bool = False):
         """device_bound: the initial incumbent from the create launch's device
-        heuristic (TSPGPU_SEARCH_DEVICE_BOUND) instead of set_bound."""
+        heuristic (TSPGPU_SEARCH_DEVICE_BOUND) instead of set_bound.
+        exhaustive: this shard of the exhaustive enumeration
+        (TSPGPU_SEARCH_EXHAUSTIVE: no bound test; for 7 <= n <= 16 one launch
+        over the prefixes p = i*nshards + shard, chain() runs it with zero
+        hooks); set_bound(a real tour's cost, the same on every shard) first.
+        Not together with device_bound (-EINVAL)."""
         self.dist, self.dtype = _search_dist(dist)
         self.n = self.dist.shape[0]
         h = ctypes.c_void_p()
+        flags = (SEARCH_DEVICE_BOUND if device_bound else 0) | (SEARCH_EXHAUSTIVE if exhaustive else 0)
         rc = lib().tspgpu_search_create_ex(ctx.handle, self.dist.ctypes.data, self.dtype, self.n, shard, nshards,
-                                           depth, 1 if device_bound else 0, ctypes.byref(h))
+                                           depth, flags, ctypes.byref(h))
         if rc:
             raise TspGpuError(rc, "tspgpu_search_create_ex")
         self.handle = h
