@@ -176,6 +176,18 @@ double tspgpu_table_bytes_per_block(int n);
 #define TSPGPU_WIDE_MAX_CITIES 31
 int tspgpu_solve_instance(tspgpu_ctx *ctx, const double *dist, int n, double *cost_out, int32_t *tour_out,
                           double *kernel_ms);
+/* K1-wide on int32 distances: the same DP, tie rule and tour layout; equals
+ * tspgpu_solve_instance on the matrix converted to double.  n in [3, 31].
+ * The table holds int32 values (half the bytes: 65 GB at n = 31), the
+ * relaxation is an integer add and min.  -EINVAL: NULL pointer, n outside
+ * [3, 31], any d < 0; -ERANGE: n * max(d) >= INT_MAX.  The context keeps one
+ * workspace per (n, value type): an f64 call after an int32 call of the same
+ * n, or the other way round, allocates anew. */
+int tspgpu_solve_instance_i32(tspgpu_ctx *ctx, const int32_t *dist, int n, int32_t *cost_out,
+                              int32_t *tour_out, double *kernel_ms);
+/* value type of the context's last K1-wide launch: TSPGPU_F64, TSPGPU_I32, -1 if none
+ * (set by both entries above and by K2's fallback; a measurement and test aid) */
+int tspgpu_wide_last_dtype(const tspgpu_ctx *ctx);
 
 /* ---------------------------------------------------------------------------
  * K2: exact search of ONE instance, prefix-parallel branch and bound over the

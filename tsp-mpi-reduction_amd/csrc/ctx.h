@@ -58,9 +58,10 @@ struct tspgpu_ctx {
     bool k1_launched = false;
     char name[256] = {0};
     std::mutex mu;
-    // K1-wide per-context cache (buffers + captured launch graph of the last n), hkwide.hip
+    // K1-wide per-context cache (buffers of the last (n, value type)), hkwide_impl.h
     void *wide_cache = nullptr;
     void (*wide_free)(void *) = nullptr;
+    int wide_last_dtype = -1;  // value type of the last K1-wide launch (tspgpu_wide_last_dtype)
     // K2 device buffers kept between searches (search_abi.cpp); null while a
     // live search holds them
     void *search_pool = nullptr;

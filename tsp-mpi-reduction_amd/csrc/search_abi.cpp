@@ -1909,12 +1909,14 @@ static int search_solve(tspgpu_ctx *c, const void *dist, int dtype, int n, doubl
         // (K1-wide, also on the GPU) gives tsp()'s tour directly for n <= 31
         if (n <= TSPGPU_WIDE_MAX_CITIES) {
             fallback = 1;
-            std::vector<double> dd(n * n);
-            if (dtype == TSPGPU_F64)
-                std::memcpy(dd.data(), dist, sizeof(double) * n * n);
-            else
-                for (int i = 0; i < n * n; ++i) dd[i] = static_cast<const int32_t *>(dist)[i];
-            rc = tspgpu_solve_instance(c, dd.data(), n, cost_out, tour_out, nullptr);
+            if (dtype == TSPGPU_F64) {
+                rc = tspgpu_solve_instance(c, static_cast<const double *>(dist), n, cost_out, tour_out, nullptr);
+            } else {
+                // integer instances stay integer: the int32 table, no widened copy
+                int32_t ci = 0;
+                rc = tspgpu_solve_instance_i32(c, static_cast<const int32_t *>(dist), n, &ci, tour_out, nullptr);
+                if (!rc) *cost_out = (double)ci;
+            }
         } else {
             rc = -EOVERFLOW;
         }

@@ -519,19 +519,24 @@ int solve_k1(const Instance &in, Result &res)
     return tspgpu_solve(d.data(), in.n, 1, &res.cost, res.tour.data(), &o);
 }
 
-// K1-wide: the DP with every CU on each layer (n <= 31); integers are exact as f64
+// K1-wide: the DP with every CU on each layer (n <= 31); integer instances
+// run on the int32 table (the same cost and tour as their f64 image)
 int solve_wide(const Instance &in, Result &res)
 {
     if (in.n > TSPGPU_WIDE_MAX_CITIES) return -EINVAL;
-    std::vector<double> d = in.d;
-    if (in.dtype == TSPGPU_I32) d.assign(in.di.begin(), in.di.end());
     res.tour.assign(in.n + 1, -1);
     tspgpu_opts o;
     std::memset(&o, 0, sizeof o);
     o.device = 0;
     tspgpu_ctx *ctx = nullptr;
     int rc = tspgpu_ctx_create(&o, &ctx);
-    if (!rc) rc = tspgpu_solve_instance(ctx, d.data(), in.n, &res.cost, res.tour.data(), &res.kernel_ms);
+    if (!rc && in.dtype == TSPGPU_I32) {
+        int32_t ci = 0;
+        rc = tspgpu_solve_instance_i32(ctx, in.di.data(), in.n, &ci, res.tour.data(), &res.kernel_ms);
+        if (!rc) res.cost = (double)ci;
+    } else if (!rc) {
+        rc = tspgpu_solve_instance(ctx, in.d.data(), in.n, &res.cost, res.tour.data(), &res.kernel_ms);
+    }
     if (ctx) tspgpu_ctx_destroy(ctx);
     return rc;
 }

@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = (
     # K3
     "tspgpu_merge", "tspgpu_reduce",
     # K1-wide
-    "tspgpu_solve_instance",
+    "tspgpu_solve_instance", "tspgpu_solve_instance_i32", "tspgpu_wide_last_dtype",
     # K1 on integer distances
     "tspgpu_validate_i32", "tspgpu_solve_blocks_i32", "tspgpu_solve_blocks_i32_device",
     # tuning / test knobs
@@ -177,6 +177,8 @@ def lib():
         L.tspgpu_tie_key.argtypes = [ctypes.c_int, ip, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         cp = ctypes.POINTER(City)
         L.tspgpu_solve_instance.argtypes = [vp, dp, ctypes.c_int, dp, ip, dp]
+        L.tspgpu_solve_instance_i32.argtypes = [vp, ip, ctypes.c_int, ip, ip, dp]
+        L.tspgpu_wide_last_dtype.argtypes = [vp]
         L.tspgpu_merge.argtypes = [vp, cp, ctypes.c_int, ctypes.c_double, cp, ctypes.c_int, ctypes.c_double, cp, dp]
         L.tspgpu_reduce.argtypes = [vp, cp, ctypes.c_int, dp, ctypes.c_int, ctypes.c_int, dp, ctypes.c_char_p,
                                     ctypes.c_int]
@@ -430,6 +432,21 @@ class Context:
         if rc:
             raise TspGpuError(rc, "tspgpu_solve_instance")
         return cost.value, tour, ms.value
+
+    def solve_instance_i32(self, dist):
+        """K1-wide on int32 distances (the int32 table) -> (int cost, tour (n+1,) int32, kernel ms)."""
+        d = np.ascontiguousarray(dist, dtype=np.int32)
+        n = d.shape[0]
+        cost, ms = ctypes.c_int32(), ctypes.c_double()
+        tour = np.zeros(n + 1, dtype=np.int32)
+        rc = lib().tspgpu_solve_instance_i32(self.handle, _ip(d), n, ctypes.byref(cost), _ip(tour), ctypes.byref(ms))
+        if rc:
+            raise TspGpuError(rc, "tspgpu_solve_instance_i32")
+        return int(cost.value), tour, ms.value
+
+    def wide_last_dtype(self) -> int:
+        """Value type of this context's last K1-wide launch (F64, I32; -1: none yet)."""
+        return lib().tspgpu_wide_last_dtype(self.handle)
 
     def merge(self, p1, c1, p2, c2):
         """K3 mergeBlocks: paths are lists of (id, x, y) -> (merged path, cost)."""
