@@ -14,7 +14,7 @@
 //   sub-cube order (members ascending, then non-members): a pass knows i and
 //   u at compile time, so d[hm_i][k] is one ds_read with an immediate offset
 //   on the lane's k, d[m][hn_u] one on the lane's m, and d[hm_i][hn_u] is
-//   wave-uniform (an SGPR operand of v_add).  Only the low-low relaxations
+//   one at a constant address (a broadcast read).  Only the low-low relaxations
 //   (43% at n = 16) keep a per-lane v_add_u32 for the address.  The extra
 //   rows/columns of sub-cube h + 1 are written by idle threads during the
 //   last pass of sub-cube h (which reads only the natural image).
@@ -26,11 +26,13 @@
 //   sub-cube h runs in the same barrier interval as j = 0/1 of sub-cube h + 1
 //   (independent work).  L - 1 = 9 intervals per sub-cube instead of 11.
 // * Row tables instead of bit loops.  A row's members, non-members and the
-//   colex ranks of its destination rows come from one 16-byte host-built
-//   entry (global, L2-resident), prefetched one pass ahead; decoding is
-//   independent v_bfe ops instead of a dependent ctz chain.
+//   finished LDS store slots of its low destinations come from one 16-byte
+//   host-built entry (sub_rows.h; global, L2-resident), prefetched one pass
+//   ahead; decoding is independent shift/mask ops instead of a dependent ctz
+//   chain, two per store slot.
 #pragma once
 #include "hk_tiled.h"
+#include "sub_rows.h"
 
 namespace tspgpu {
 
@@ -44,13 +46,8 @@ namespace tspgpu {
 #endif
 __host__ __device__ constexpr int sub_ds(int L) { return L >= 10 ? TSPGPU_SUB_DS : 23; }
 
-// one entry per L-bit mask (indexed like TiledInfo::mask, L <= 10): nibbles
-// 0..L-1 = the members ascending, then the non-members ascending; bytes
-// 5..14 = colex rank of mask | (1 << k_q) among the masks of one more member,
-// for the q-th non-member k_q
-struct SubRow {
-    uint32_t w[4];
-};
+// (SubRow, one 16-byte entry per L-bit mask indexed like TiledInfo::mask, and
+// its bit layout: sub_rows.h)
 
 __host__ __device__ constexpr size_t sub_img_bytes(int N, int L, int vb)
 {
@@ -97,60 +94,6 @@ template <typename V>
 __device__ __forceinline__ V lds_val(const char *base, uint32_t byte_off)
 {
     return *reinterpret_cast<const V *>(base + byte_off);
-}
-// wave-uniform LDS value -> SGPR(s)
-template <typename V>
-__device__ __forceinline__ V uniform_val(const char *base, uint32_t byte_off)
-{
-    const V v = lds_val<V>(base, byte_off);
-    if constexpr (sizeof(V) == 8) {
-        const uint64_t u = __builtin_bit_cast(uint64_t, v);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return __builtin_bit_cast(V, ((uint64_t)hi << 32) | lo);
-    } else {
-        return (V)__builtin_amdgcn_readfirstlane((uint32_t)v);
-    }
-}
-
-// relaxations whose distance is an SGPR operand (wave-uniform)
-__device__ __forceinline__ void relax_min_s(double &acc, double g, double d)
-{
-    double t;
-    asm volatile("v_add_f64 %[t], %[g], %[d]\n\tv_min_f64 %[acc], %[acc], %[t]"
-                 : [acc] "+v"(acc), [t] "=&v"(t)
-                 : [g] "v"(g), [d] "s"(d));
-}
-__device__ __forceinline__ void relax_min_s(int32_t &acc, int32_t g, int32_t d)
-{
-    int32_t t;
-    asm volatile("v_add_u32 %[t], %[d], %[g]\n\tv_min_i32 %[acc], %[acc], %[t]"
-                 : [acc] "+v"(acc), [t] "=&v"(t)
-                 : [g] "v"(g), [d] "s"(d));
-}
-__device__ __forceinline__ void relax_argmin_s(double &acc, uint32_t &arg, double g, double d, uint32_t m)
-{
-    double t;
-    asm volatile(
-        "v_add_f64 %[t], %[g], %[d]\n\t"
-        "v_cmp_lt_f64 vcc, %[t], %[acc]\n\t"
-        "v_cndmask_b32 %[arg], %[arg], %[m], vcc\n\t"
-        "v_min_f64 %[acc], %[acc], %[t]"
-        : [acc] "+v"(acc), [arg] "+v"(arg), [t] "=&v"(t)
-        : [g] "v"(g), [d] "s"(d), [m] "v"(m)
-        : "vcc");
-}
-__device__ __forceinline__ void relax_argmin_s(int32_t &acc, uint32_t &arg, int32_t g, int32_t d, uint32_t m)
-{
-    int32_t t;
-    asm volatile(
-        "v_add_u32 %[t], %[d], %[g]\n\t"
-        "v_cmp_lt_i32 vcc, %[t], %[acc]\n\t"
-        "v_cndmask_b32 %[arg], %[arg], %[m], vcc\n\t"
-        "v_min_i32 %[acc], %[acc], %[t]"
-        : [acc] "+v"(acc), [arg] "+v"(arg), [t] "=&v"(t)
-        : [g] "v"(g), [d] "s"(d), [m] "v"(m)
-        : "vcc");
 }
 
 // two / four independent min-only relaxations in one block: every add is
@@ -236,11 +179,13 @@ __device__ __forceinline__ uint32_t sub_nib(const uint4 &e, int i)
 {
     return i < 8 ? (e.x >> (4 * i)) & 15u : (e.y >> (4 * (i - 8))) & 15u;
 }
-__device__ __forceinline__ uint32_t sub_rank(const uint4 &e, int q)
+// the finished slot of the q-th low destination in the next low layer (sub_rows.h)
+template <int L, int J>
+__device__ __forceinline__ uint32_t sub_slot(const uint4 &e, int q)
 {
-    const int b = 5 + q;  // byte index
-    const uint32_t w = b < 4 ? e.x : (b < 8 ? e.y : (b < 12 ? e.z : e.w));
-    return (w >> (8 * (b & 3))) & 255u;
+    const int pos = sub_slot_pos(L, J, q);
+    const uint32_t w = pos < 32 ? e.x : (pos < 64 ? e.y : (pos < 96 ? e.z : e.w));
+    return (w >> (pos & 31)) & ((1u << sub_slot_bits(L, J)) - 1u);
 }
 
 // ---------------------------------------------------------------------------
@@ -250,67 +195,42 @@ __device__ __forceinline__ uint32_t sub_rank(const uint4 &e, int q)
 // members ascending of G[T][m] + d[m][k] (tsp.cpp:457-470), argmin kept only
 // in the top rows (T >= N - TSPGPU_TILED_TA_OFF).
 // ---------------------------------------------------------------------------
-// relaxation order of a destination chunk [C0, C0 + QN): every (member,
-// destination) pair whose distance comes from LDS, member-major, then the
-// high-high pairs (SGPR distances) — per destination still members ascending
-template <int T, int J, int QL, int C0, int QN>
-__host__ __device__ constexpr int sub_lds_count()
-{
-    int n = 0;
-    for (int p = 0; p < T; ++p)
-        for (int qq = 0; qq < QN; ++qq)
-            if (!(p >= J && C0 + qq >= QL)) ++n;
-    return n;
-}
+// relaxation order of a destination chunk of QN destinations: all T x QN
+// (member, destination) pairs, every distance an LDS read (the high-high ones
+// too: a broadcast read of the sub-cube-ordered image) — per destination the
+// members ascending.
 // QP = false: member-major (p, then the destinations q: consecutive
 // relaxations have different destinations, independent min chains).  QP =
 // true (integer values): member 0's row first, then member PAIRS (p, p + 1)
 // destination by destination, so relaxations 2i-1 and 2i share q and fold
 // into one v_min3 (acc = min3(acc, g_p + d, g_(p+1) + d')).
-template <int T, int J, int QL, int C0, int QN, bool QP = false>
+// Returns p * 64 + q of relaxation k.
+template <int T, int QN, bool QP = false>
 __host__ __device__ constexpr int sub_lds_pair(int k)
 {
-    int n = 0;
-    if (!QP) {
-        for (int p = 0; p < T; ++p)
-            for (int qq = 0; qq < QN; ++qq)
-                if (!(p >= J && C0 + qq >= QL)) {
-                    if (n == k) return p * 64 + qq;
-                    ++n;
-                }
-        return -1;
-    }
-    for (int qq = 0; qq < QN; ++qq)
-        if (!(0 >= J && C0 + qq >= QL)) {
-            if (n == k) return qq;
-            ++n;
-        }
+    if (!QP) return (k / QN) * 64 + k % QN;
+    if (k < QN) return k;
+    int n = QN;
     for (int p = 1; p < T; p += 2)
         for (int qq = 0; qq < QN; ++qq)
-            for (int pp = p; pp < p + 2 && pp < T; ++pp)
-                if (!(pp >= J && C0 + qq >= QL)) {
-                    if (n == k) return pp * 64 + qq;
-                    ++n;
-                }
+            for (int pp = p; pp < p + 2 && pp < T; ++pp) {
+                if (n == k) return pp * 64 + qq;
+                ++n;
+            }
     return -1;
 }
 
 // QP order: 1 = relaxation k opens a same-destination member pair (k, k + 1),
-// 2 = k closes one, 0 = a single relaxation (member 0, or a pair member whose
-// partner is a high-high relaxation, which is not in the LDS list)
-template <int T, int J, int QL, int C0, int QN>
+// 2 = k closes one, 0 = a single relaxation (member 0, or the last member
+// when it has no partner)
+template <int T, int QN>
 __host__ __device__ constexpr int sub_lds_role(int k)
 {
-    int n = 0;
-    for (int qq = 0; qq < QN; ++qq)
-        if (!(0 >= J && C0 + qq >= QL)) {
-            if (n == k) return 0;
-            ++n;
-        }
+    if (k < QN) return 0;
+    int n = QN;
     for (int p = 1; p < T; p += 2)
         for (int qq = 0; qq < QN; ++qq) {
-            int in = 0;
-            for (int pp = p; pp < p + 2 && pp < T; ++pp) in += !(pp >= J && C0 + qq >= QL) ? 1 : 0;
+            const int in = p + 1 < T ? 2 : 1;
             for (int i = 0; i < in; ++i, ++n)
                 if (n == k) return in == 2 ? 1 + i : 0;
         }
@@ -340,6 +260,10 @@ __device__ __forceinline__ uint32_t sub_col(uint32_t hp, uint32_t x)
 // push loads issued early (+18%: they wait behind older stores in the in-order
 // vmcnt), rotated wave roles, scalar loads of the high-high distances (+60%),
 // one |h| dispatch per sub-cube, a workgroup-form backtracking (no faster).
+// Replaced in round 7 (profiles/r07/k1_bookkeeping): row entries with rank
+// bytes, the slot rebuilt per destination (4 VALU instead of 2; +2% forward
+// time), and the high-high distances as SGPR operands fetched with two
+// v_readfirstlane each at the top of every pass by all four waves (+2%).
 
 template <typename V, int N, int L, int T, int J>
 __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, uint32_t tid, const uint4 &ent)
@@ -354,7 +278,6 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
     constexpr int VB = sizeof(V);
     constexpr int ROWS = cbinom(L, J);
     constexpr int BASE = tiled_moff(L, J);
-    constexpr int ROWS_N = cbinom(L, J + 1);
     constexpr int CUR = sub_layer_off(L, J);
     constexpr int NXT = sub_layer_off(L, J + 1);
     constexpr bool ARG = T >= N - TSPGPU_TILED_TA_OFF;
@@ -376,12 +299,6 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
             nb &= nb - 1u;
         }
     }
-    // high-high distances of this sub-cube: wave-uniform, from the LDS image
-    V hh[HC * QH > 0 ? HC * QH : 1];
-#pragma unroll
-    for (int i = 0; i < HC; ++i)
-#pragma unroll
-        for (int u = 0; u < QH; ++u) hh[i * QH + u] = uniform_val<V>(c.img, HR0 + i * DSB + HC0 + u * VB);
     const uint32_t r = tid;
     const bool act = r < (uint32_t)ROWS;
     V g[T];
@@ -410,7 +327,7 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
     static_for<(Q + QC - 1) / QC>([&](auto ci) {
         constexpr int C0 = decltype(ci)::value * QC;
         constexpr int QN = Q - C0 < QC ? Q - C0 : QC;
-        constexpr int CNT = sub_lds_count<T, J, QL, C0, QN>();
+        constexpr int CNT = T * QN;
         constexpr int AH = kSubAhead < CNT ? kSubAhead : CNT;
         // integer min-only rows: member pairs per destination (v_min3_i32)
         constexpr bool QP = !ARG && std::is_same<V, int32_t>::value;
@@ -418,21 +335,23 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
         uint32_t arg[ARG ? QN : 1];
         // distance of LDS relaxation k (compile-time pair)
         auto dload = [&](auto kk) -> V {
-            constexpr int pq = sub_lds_pair<T, J, QL, C0, QN, QP>(decltype(kk)::value);
+            constexpr int pq = sub_lds_pair<T, QN, QP>(decltype(kk)::value);
             constexpr int p = pq / 64, q = C0 + pq % 64;
             if constexpr (p < J && q < QL)
                 return lds_val<V>(c.img, mrow[p] + kof[q]);
             else if constexpr (p < J)
                 return lds_val<V>(c.img, mrow[p] + HC0 + (q - QL) * VB);
-            else
+            else if constexpr (q < QL)
                 return lds_val<V>(c.img, HR0 + (p - J) * DSB + kof[q]);
+            else  // high-high: the same address in every lane (a broadcast read)
+                return lds_val<V>(c.img, HR0 + (p - J) * DSB + HC0 + (q - QL) * VB);
         };
         V dv[AH > 0 ? AH : 1];
         static_for<AH>([&](auto kk) { dv[decltype(kk)::value] = dload(kk); });
         // relaxation k of the chunk (its distance from the load pipeline)
         auto relax_one = [&](auto kk) {
             constexpr int k = decltype(kk)::value;
-            constexpr int pq = sub_lds_pair<T, J, QL, C0, QN, QP>(k);
+            constexpr int pq = sub_lds_pair<T, QN, QP>(k);
             constexpr int p = pq / 64, qq = pq % 64;
             const V d = dv[k % AH];
             if constexpr (k + AH < CNT) dv[k % AH] = dload(std::integral_constant<int, k + AH>{});
@@ -449,10 +368,10 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
         if constexpr (QP) {
             static_for<CNT>([&](auto kk) {
                 constexpr int k = decltype(kk)::value;
-                constexpr int role = sub_lds_role<T, J, QL, C0, QN>(k);
+                constexpr int role = sub_lds_role<T, QN>(k);
                 if constexpr (role == 1) {
-                    constexpr int pq0 = sub_lds_pair<T, J, QL, C0, QN, QP>(k);
-                    constexpr int pq1 = sub_lds_pair<T, J, QL, C0, QN, QP>(k + 1);
+                    constexpr int pq0 = sub_lds_pair<T, QN, QP>(k);
+                    constexpr int pq1 = sub_lds_pair<T, QN, QP>(k + 1);
                     static_assert(pq0 % 64 == pq1 % 64 && pq1 / 64 == pq0 / 64 + 1, "member pair");
                     const V d0 = dv[k % AH];
                     if constexpr (k + AH < CNT) dv[k % AH] = dload(std::integral_constant<int, k + AH>{});
@@ -469,8 +388,8 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
         } else if constexpr (!ARG) {
             static_for<(CNT + 1) / 2>([&](auto kk2) {
                 constexpr int k0 = 2 * decltype(kk2)::value, k1 = k0 + 1;
-                constexpr int pq0 = sub_lds_pair<T, J, QL, C0, QN, QP>(k0);
-                constexpr int pq1 = k1 < CNT ? sub_lds_pair<T, J, QL, C0, QN, QP>(k1) : 0;
+                constexpr int pq0 = sub_lds_pair<T, QN, QP>(k0);
+                constexpr int pq1 = k1 < CNT ? sub_lds_pair<T, QN, QP>(k1) : 0;
                 constexpr int p0 = pq0 / 64, q0 = pq0 % 64, p1 = pq1 / 64, q1 = pq1 % 64;
                 if constexpr (k1 < CNT && p0 > 0 && p1 > 0 && q0 != q1) {
                     const V d0 = dv[k0 % AH];
@@ -490,27 +409,12 @@ __device__ __forceinline__ void sub_mid(const SubCtx<V, N, L> &c, uint32_t h, ui
                 __builtin_amdgcn_sched_barrier(0);
             });
         }
-        // high members x high destinations: SGPR distances
-#pragma unroll
-        for (int i = 0; i < HC; ++i)
-#pragma unroll
-            for (int qq = 0; qq < QN; ++qq) {
-                const int q = C0 + qq;
-                if (q >= QL) {
-                    if constexpr (ARG)
-                        relax_argmin_s(acc[qq], arg[qq], g[J + i], hh[i * QH + (q - QL)], hrow[i]);
-                    else
-                        relax_min_s(acc[qq], g[J + i], hh[i * QH + (q - QL)]);
-                }
-            }
 #pragma unroll
         for (int qq = 0; qq < QN; ++qq) {
             const int q = C0 + qq;
             if (q < QL) {
-                // low k -> next LDS layer: position k - q, colex rank of l + k
-                const uint32_t k = kof[q] / VB;
-                const uint32_t slot = (k - (uint32_t)q) * (uint32_t)ROWS_N + sub_rank(ent, q);
-                c.region[NXT + slot] = acc[qq];
+                // low k -> next LDS layer: position k - q, colex rank of l + k (the entry's slot field)
+                c.region[NXT + sub_slot<L, J>(ent, q)] = acc[qq];
             } else {
                 // high k -> push column (h | k, k) of sub-cube h | k, same row index
                 const uint32_t cb = hn[q - QL];

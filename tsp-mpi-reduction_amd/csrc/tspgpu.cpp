@@ -239,40 +239,15 @@ int split_begin(tspgpu_ctx *c, hipStream_t stream, size_t *ev0)
     return hipEventRecord(c->ev_split[*ev0], stream) == hipSuccess ? 0 : -EIO;
 }
 
-// Variant 6 row table of L (hk_sub.h SubRow): per L-bit mask, its members
-// then non-members as nibbles, and the colex rank of mask | (1 << k) for every
-// non-member k (the destination row of the next low layer).
+// Variant 6 row table of L (sub_rows.h, built by sub_rows.cpp), uploaded once.
 int ensure_sub_rows(tspgpu_ctx *c, int L)
 {
-    if (L > 10) return -EINVAL;  // 8-bit ranks: C(10, 5) = 252
+    if (L < 0 || L >= 16) return -EINVAL;
     if (c->d_subrows[L]) return 0;
+    std::vector<SubRow> rows;
+    if (!build_sub_rows(L, rows)) return -EINVAL;
     int rc = ensure_tiled_info(c, L);
     if (rc) return rc;
-    std::vector<int> rank(1 << L, 0);
-    std::vector<uint32_t> order;  // masks by (popcount, value) = TiledInfo::mask
-    for (int j = 0; j <= L; ++j) {
-        int r = 0;
-        for (uint32_t m = 0; m < (1u << L); ++m)
-            if (__builtin_popcount(m) == j) {
-                rank[m] = r++;
-                order.push_back(m);
-            }
-    }
-    std::vector<SubRow> rows(order.size());
-    for (size_t i = 0; i < order.size(); ++i) {
-        const uint32_t m = order[i];
-        uint8_t bytes[16] = {0};
-        int slot = 0, q = 0;
-        auto put_nib = [&](int idx, uint32_t v) { bytes[idx / 2] |= (uint8_t)(v << (4 * (idx & 1))); };
-        for (int b = 0; b < L; ++b)
-            if (m >> b & 1) put_nib(slot++, (uint32_t)b);
-        for (int b = 0; b < L; ++b)
-            if (!(m >> b & 1)) {
-                put_nib(slot++, (uint32_t)b);
-                bytes[5 + q++] = (uint8_t)rank[m | (1u << b)];
-            }
-        std::memcpy(rows[i].w, bytes, 16);
-    }
     void *d = nullptr;
     hipError_t e = hipMalloc(&d, rows.size() * sizeof(SubRow));
     if (e == hipSuccess) e = upload_sync(c, d, rows.data(), rows.size() * sizeof(SubRow));
