@@ -145,19 +145,17 @@ def test_tiny_budget_splits_everything(gpu_ctx, budget, knobs):
             assert st["rounds"] > 2, st
 
 
-@pytest.mark.parametrize("mode", ["donate_always", "small_ring", "kernel1", "kernel2"])
-def test_search_kernels_and_hand_off_stress(gpu_ctx, mode, knobs):
-    """Persistent search with a donation at every chance (every busy lane
-    splits its root level whenever it may), with a 64-item ring (donations
-    mostly refused by the capacity check), and the two round kernels: same
-    cost and tour as the oracle, tie-heavy and random instances."""
-    env = {"donate_always": {"SEARCH_HUNGRY": "-1000000000", "SEARCH_MIN_SPLIT": "0"},
-           "small_ring": {"SEARCH_RING_LOG2": "6", "SEARCH_HUNGRY": "-1000000000", "SEARCH_MIN_SPLIT": "0"},
-           "kernel1": {"SEARCH_KERNEL": "1"}, "kernel2": {"SEARCH_KERNEL": "2"}}[mode]
-    for k, v in env.items():
-        knobs.set(k, v)
-    knobs.set("SEARCH_WALL_S", "30")
-    rng = np.random.default_rng(len(mode))
+@pytest.mark.parametrize("kernel,seed", [(None, 13), (None, 10), ("1", 7), ("2", 7)],
+                         ids=["default_seed13", "default_seed10", "kernel1", "kernel2"])
+def test_search_kernels_and_hand_off_stress(gpu_ctx, kernel, seed, knobs):
+    """search_solve with the default settings (two instance sets) and with
+    each round kernel named by SEARCH_KERNEL (1: branching DFS, 2: lock-step
+    DFS): same cost and tour as the oracle, tie-heavy and random instances,
+    n = 5..14."""
+    mode = "default" if kernel is None else "kernel" + kernel
+    if kernel is not None:
+        knobs.set("SEARCH_KERNEL", kernel)
+    rng = np.random.default_rng(seed)
     for n in (5, 9, 12, 14):
         for kind in ("ties", "random"):
             if kind == "ties":
@@ -682,3 +680,41 @@ def test_device_bound_and_record_certificate(gpu_ctx, knobs, n, seed):
         assert rc_r == rc_g == 0 and t_r.tolist() == t_g.tolist() == want[1].tolist()
     finally:
         S.close()
+
+
+def test_pooled_buffers_across_searches(knobs):
+    """One context, five searches in a row: every search takes the buffers its
+    predecessor gave back to the context's pool, at other capacities (a default
+    solve, the enum kernel without frontier buffers, a frontier search with a
+    256-slot tail buffer — seed depth 2, so that 13 cities have levels to
+    expand and the tail buffer is reallocated — an integer instance, the first
+    instance again, its tail buffer reallocated at the default size): each the
+    oracle's cost and tour, the last one the first one's."""
+    rng = np.random.default_rng(2308)
+
+    def points(n):
+        xy = rng.uniform(0, 1000, size=(n, 2))
+        return O.distance_matrix([(i, xy[i, 0], xy[i, 1]) for i in range(n)])
+
+    d14, d9, d13 = points(14), points(9), points(13)
+    m12 = rng.integers(1, 1000, size=(12, 12)).astype(np.int32)
+    m12 = np.minimum(m12, m12.T)
+    np.fill_diagonal(m12, 0)
+    with tspgpu.Context(device=0) as ctx:
+        def solve(d, step, **kw):
+            cost, tour, st = tspgpu.search_solve(ctx, d, **kw)
+            oc, ot = O.solve_block(np.asarray(d, dtype=np.float64))
+            assert (float(cost), tour.tolist()) == (oc, ot), (step, st)
+            return cost, tour.tolist(), st
+
+        first = solve(d14, 1)
+        assert first[2]["depth"] < 14 - 1 - 6, first[2]  # (a frontier search: levels above the 6-city tails)
+        solve(d9, 2, exhaustive=True)
+        knobs.set("SEARCH_TAIL_CAP_LOG2", "8")
+        knobs.set("SEARCH_DEPTH", "2")
+        st3 = solve(d13, 3)[2]
+        knobs.clear("SEARCH_TAIL_CAP_LOG2")
+        knobs.clear("SEARCH_DEPTH")
+        assert st3["depth"] == 2, st3  # (2 < 13 - 1 - 6: a frontier search, so the tail buffer is in use)
+        solve(m12, 4)
+        assert solve(d14, 5)[:2] == first[:2]

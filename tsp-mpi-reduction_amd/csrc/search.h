@@ -36,24 +36,6 @@ struct alignas(16) PathItem {
     uint8_t b[32];
 };
 
-// Device words of the persistent search (search_persist_kernel), zeroed by
-// the host before every launch except work = this shard's seed count.  Each
-// word has a 256-byte line of its own: the counters take atomics from every
-// wave and idle waves poll `work`, so sharing a line would serialise them.
-struct alignas(256) PersistWord {
-    unsigned long long v;
-    unsigned long long pad[31];
-};
-struct PersistState {
-    PersistWord seed_cursor;  // next seed (index into this shard's prefixes)
-    PersistWord head;         // ring tickets claimed by lanes
-    PersistWord tail;         // ring tickets reserved by donors
-    PersistWord consumed;     // ring items read
-    PersistWord work;         // items created (seeds + donations) and not finished
-    PersistWord abort;        // 1: watchdog, 2: ring lapped (never expected)
-};
-constexpr int kRingWords = 5;  // ring item: 4 words of city bytes + (ticket+1) << 32 | from << 8 | len
-
 struct SearchArgs {
     const void *dist;          // n*n row-major, f64 or i32 (device)
     const void *amin;          // n: cheapest edge entering each city (device), f64 on a 2^-20 grid or i32
@@ -73,18 +55,26 @@ struct SearchArgs {
     unsigned int rec_cap;
     // statistics: kStatLines lines of kStatStride u64, a block adds to line
     // blockIdx % kStatLines (one hot address serialises device atomics):
-    // [0] search nodes evaluated, v2: [1] lane slots, [2] active lane steps, [3] item loads
+    // [0] search nodes evaluated, kernel 2: [1] lane slots, [2] active lane steps, [3] item loads
     unsigned long long *nodes;
-    uint32_t refill;           // v2: a wave refills once this many lanes wait for an item
-    // persistent search (kernel 3)
-    PersistState *ps;
-    unsigned long long *ring;  // kRingWords u64 per item
-    uint32_t ring_mask;        // capacity - 1 (power of two)
-    uint32_t ring_margin;      // reservations stop this far below capacity
-    int32_t hungry;            // donate while more than this many lanes wait for unreserved tickets
-    uint32_t min_split;        // steps on an item before it may donate
-    unsigned long long wall_limit;  // watchdog, wall_clock64 ticks
-    int kernel;                // round kernel: 2 (lock-step DFS, default) or 1 (branching DFS); 3 = persistent
+    uint32_t refill;           // kernel 2: a wave refills once this many lanes wait for an item
+    // (the next five sit here so that `fin` and what follows keep their kernarg
+    // offsets: profiles/r08/k2_host_refactor/k2_phase_medians.txt)
+    // device tie rule (TieSlot below; null: records only)
+    struct TieSlot *tie;
+    uint32_t tie_mask;         // slots - 1 (power of two)
+    unsigned int *tie_overflow;
+    // chained searches: the prologue's block 0 stores the device wall clock
+    // (wall_clock64) here at its start, the fetch kernel its own beside it, so
+    // the chain is timed without events (an event costs ~5 us of the GPU's
+    // timeline between two launches); null: not stored
+    unsigned long long *t_start;
+    // enum_kernel: the partial paths of the prefix levels above its lanes
+    // (sum of N!/(N-l)!, l = 1..N-6; host-computed), added to the node
+    // statistic once per launch — by shard 0 only, so the shards' nodes sum to
+    // the one-shard count
+    unsigned long long enum_upper;
+    int kernel;                // round kernel: 2 (lock-step DFS, default) or 1 (branching DFS)
     int noprune;               // exhaustive enumeration: no bound test (kernels 2 and seed only)
     int tails;                 // kernel 2: last four cities enumerated in registers (tail4)
     // frontier search (expand_kernel + tail_kernel): fin is expanded one
@@ -144,20 +134,6 @@ struct SearchArgs {
     const double *hsuf;
     int hs_len;
     uint32_t hs_off[8];
-    // device tie rule (TieSlot below; null: records only)
-    struct TieSlot *tie;
-    uint32_t tie_mask;         // slots - 1 (power of two)
-    unsigned int *tie_overflow;
-    // chained searches: the prologue's block 0 stores the device wall clock
-    // (wall_clock64) here at its start, the fetch kernel its own beside it, so
-    // the chain is timed without events (an event costs ~5 us of the GPU's
-    // timeline between two launches); null: not stored
-    unsigned long long *t_start;
-    // enum_kernel: the partial paths of the prefix levels above its lanes
-    // (sum of N!/(N-l)!, l = 1..N-6; host-computed), added to the node
-    // statistic once per launch — by shard 0 only, so the shards' nodes sum to
-    // the one-shard count
-    unsigned long long enum_upper;
     hipStream_t stream;
 };
 
@@ -279,7 +255,6 @@ hipError_t launch_enum(const SearchArgs &a, bool f64, int grid);
 hipError_t launch_to_paths(const SearchArgs &a);  // a.in (seeds) -> a.fout
 hipError_t launch_expand(const SearchArgs &a, bool f64);
 hipError_t launch_tail(const SearchArgs &a, bool f64, int grid);
-hipError_t launch_persist(const SearchArgs &a, bool f64, int grid);
 // the tie slot of *cost (null: of the incumbent) -> out[0..4] (search.hip
 // tie_lookup_kernel): found, w0, the sub-slot's (w0, w1), overflow
 hipError_t launch_tie_lookup(const SearchArgs &a, unsigned long long *out, const unsigned long long *cost = nullptr);

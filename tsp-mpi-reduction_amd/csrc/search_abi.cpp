@@ -49,11 +49,111 @@ using tspgpu::tuned_or;
 static_assert(sizeof(SearchRecord) == sizeof(tspgpu_tour_record), "record layout");
 constexpr int kWords = 16;  // device counter words of a search (see tspgpu_search::d_words)
 constexpr size_t kStatBytes = sizeof(unsigned long long) * kStatLines * kStatStride;
+constexpr size_t kTieBytes = sizeof(TieSlot) * kTieSlots;  // the tie slots; 8 words follow them
 constexpr size_t kStageSpec = 24 * 1024;  // h_stage: tables below, speculative records above
 constexpr unsigned kSpecRecs = 512;
 constexpr size_t kStageBytes = kStageSpec + 8 * kFetchWords + sizeof(SearchRecord) * kSpecRecs;
 
-struct tspgpu_search {
+namespace {
+
+// Move-only owner of one HIP handle and its capacity (in the owner's unit):
+// a move leaves the source null with capacity 0, the destructor frees.  Frees
+// need the search's device current: tspgpu_search_destroy and the context's
+// release set it before they drop a SearchBuffers.
+template <typename P, auto Free>
+struct Owned {
+    P p = nullptr;
+    size_t cap = 0;
+    Owned() = default;
+    Owned(Owned &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    Owned &operator=(Owned &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void reset()
+    {
+        if (p) (void)Free(p);
+        p = nullptr, cap = 0;
+    }
+    operator P() const { return p; }
+};
+template <typename T>
+using DevBuf = Owned<T *, hipFree>;
+template <typename T>
+using Pinned = Owned<T *, hipHostFree>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// (re)allocate b for `count` elements
+template <typename T>
+hipError_t dev_alloc(DevBuf<T> &b, size_t count)
+{
+    b.reset();
+    hipError_t e = hipMalloc((void **)&b.p, count * sizeof(T));
+    if (e == hipSuccess) b.cap = count;
+    return e;
+}
+template <typename T>
+hipError_t pinned_alloc(Pinned<T> &b, size_t count)
+{
+    b.reset();
+    hipError_t e = hipHostMalloc((void **)&b.p, count * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) b.cap = count;
+    return e;
+}
+
+}  // namespace
+
+// Every device buffer, pinned host buffer and event of a search — the ONE list
+// of them.  A context keeps the set of its last search between searches
+// (hipMalloc of the tail and frontier buffers costs more than a 16-city search
+// itself): the next search takes it (take_pool), its destroy gives it back.
+struct SearchBuffers {
+    DevBuf<double> d_dist, d_amin;  // (f64 or i32 values; sized for doubles)
+    // [0] queue (u32), [1] incumbent, [2] nodes, [3] record count (u32), [4] items out / seed
+    // count (u32), [5..7] utilisation counters, [8] tail items (u32), [9] odd frontier steps'
+    // child count (u32), [10..12] chained level counters (u32, in rotation), [13] chained
+    // overflow flag (u32), [14] the incumbent a chain started from (its rerun restores it),
+    // [15] a chain's start: the device wall clock (SearchArgs::t_start)
+    DevBuf<unsigned long long> d_words;
+    DevBuf<unsigned long long> d_stats;  // kStatLines x kStatStride: [0] nodes, [1..3] lane-step counters
+    DevBuf<SearchRecord> d_rec;          // (cap: records it holds)
+    DevBuf<SearchItem> d_items[2];       // round input / output (ping-pong)
+    // stronger frontier bounds (SearchArgs::bnd2 / ::mst / ::hsuf)
+    DevBuf<double> d_bnd2, d_mst, d_hsuf;
+    // The frontier is a LIFO stack of segments, each a run of paths in its own
+    // buffer (fb): a step expands the top T items of the top segment and its
+    // children become a new segment on top, written straight into a spare
+    // buffer (no device copy of the children behind the items left below:
+    // those copies were 11 ms of a 61 ms 30-city search).
+    std::vector<DevBuf<PathItem>> fb;
+    DevBuf<PathItem> d_tail;
+    // device tie rule (search.h): kTieSlots slots, then 8 words: [0..4] the
+    // optimum's slot (tie_lookup_kernel), [5] the overflow flag
+    DevBuf<TieSlot> d_tie;
+    Event e0, e1, e2;
+    Pinned<unsigned long long> h_cnt;  // pinned host words: the frontier step's counter readback
+    // pinned host copy of the statistics lines + 8 counter words (one DMA
+    // pair and one synchronisation per counters read)
+    Pinned<unsigned long long> h_stats;
+    // pinned staging: the host tables of create (so their copies need no
+    // synchronisation) and, at kStageSpec, the speculative records readback
+    Pinned<char> h_stage;
+    SearchBuffers() = default;
+    SearchBuffers(SearchBuffers &&) = default;
+    SearchBuffers &operator=(SearchBuffers &&) = default;
+};
+
+struct tspgpu_search : SearchBuffers {
+    // the knobs the host plan reads (search_host.h): kernel (SEARCH_KERNEL: 2
+    // lock-step DFS, 1 branching DFS), tail_len (SEARCH_TAIL), use_two_edge,
+    // use_lagrange, use_mst, mst_min_rem
+    tspgpu::host::PlanOptions opt;
     tspgpu_ctx *ctx = nullptr;
     int n = 0;
     int dtype = TSPGPU_F64;
@@ -62,36 +162,11 @@ struct tspgpu_search {
     uint64_t local_items = 0;  // prefixes of this shard
     uint32_t shard = 0, nshards = 1;
     int grid = 0;
-    std::vector<double> hd;    // host copy (f64 view) for the selection
-    std::vector<int32_t> hi;
-    void *d_dist = nullptr, *d_amin = nullptr;
-    // [0] queue (u32), [1] incumbent, [2] nodes, [3] record count (u32), [4] items out / seed
-    // count (u32), [5..7] utilisation counters, [8] tail items (u32), [9] odd frontier steps'
-    // child count (u32), [10..12] chained level counters (u32, in rotation), [13] chained
-    // overflow flag (u32), [14] the incumbent a chain started from (its rerun restores it),
-    // [15] a chain's start: the device wall clock (SearchArgs::t_start)
-    unsigned long long *d_words = nullptr;
-    unsigned long long *d_stats = nullptr;  // kStatLines x kStatStride: [0] nodes, [1..3] lane-step counters
-    SearchRecord *d_rec = nullptr;
     unsigned int rec_cap = 0;    // records the kernels may write
-    unsigned int rec_alloc = 0;  // records d_rec holds
-    SearchItem *d_items[2] = {nullptr, nullptr};  // round input / output (ping-pong)
-    size_t item_cap[2] = {0, 0};
     int cur = 0;                 // d_items[cur] holds the pending items
     uint64_t pending = 0;        // items waiting for the next round
     uint32_t budget = 256;       // DFS iterations per item per round
-    uint32_t refill = 16;        // v2/persistent: refill a wave once this many lanes wait
-    // round kernel (knob SEARCH_KERNEL): 2 lock-step DFS (default), 1 branching DFS;
-    // 3 = run_all as ONE persistent launch with a device work ring (measured
-    // 1.3-2x slower than rounds at n = 18: profiles/r01/k2_persistent.log)
-    int kernel = 2;
-    // persistent search
-    PersistState *d_ps = nullptr;
-    unsigned long long *d_ring = nullptr;
-    uint32_t ring_cap = 1u << 20;
-    int32_t hungry = 0;
-    uint32_t min_split = 64;
-    double wall_s = 300.0;
+    uint32_t refill = 16;        // lock-step DFS: refill a wave once this many lanes wait
     int noprune = 0;             // exhaustive enumeration (tspgpu_search_enumerate)
     int enum_kernel = 0;         // enumeration by enum.hip (6-city register tails, 7 <= n <= 16)
     // Frontier search (default for the bounded search when n - 1 - tail_len >
@@ -101,61 +176,32 @@ struct tspgpu_search {
     // collect in d_tail and are folded by tail_kernel, all tail_len!
     // completions in registers, once tail_cap / 2 of them wait or the
     // frontier is empty.
-    int tail_len = 6;
     bool frontier = false;
     bool chain = true;  // run_all: small searches as chained levels (knob SEARCH_CHAIN=0: step by step)
-    // stronger frontier bounds (SearchArgs::bnd2 / ::hsuf): the two-edge bound
-    // for symmetric matrices and the suffix table for the last tail_len cities
+    // the two-edge bound for symmetric matrices and the suffix table for the
+    // last tail_len cities
     int sym = 0;
-    void *d_bnd2 = nullptr;
-    double *d_mst = nullptr;
-    double *d_hsuf = nullptr;
-    size_t hsuf_alloc = 0;      // bytes
     int hs_len = 0;             // sizes 1..hs_len built (0: none)
     uint32_t hs_off[8] = {};
     int suffix_len = 6;         // knob SEARCH_SUFFIX=0/5/6: table size (0: B0/B1 only)
-    bool use_two_edge = true;   // knob SEARCH_TWO_EDGE=0: no B1
-    bool use_lagrange = true;   // knob SEARCH_LAGRANGE=0: B1 without the Lagrangian city weights
-    bool use_mst = true;        // knob SEARCH_MST=0: no Held-Karp tree bound in the expand kernel
-    bool mst_on = false;        // (symmetric matrices only)
-    int mst_min_rem = 12;       // knob SEARCH_MST_MINREM: paths with fewer cities left skip it (measured: profiles/r02/k2_tree_minrem.log)
-    // The frontier is a LIFO stack of segments, each a run of paths in its own
-    // buffer (fb): a step expands the top T items of the top segment and its
-    // children become a new segment on top, written straight into a spare
-    // buffer (no device copy of the children behind the items left below:
-    // those copies were 11 ms of a 61 ms 30-city search).
-    std::vector<PathItem *> fb;       // frontier buffers (kept in the context's pool between searches)
-    std::vector<size_t> fb_cap;
-    std::vector<int> seg_buf;         // buffer index of each segment, bottom first
+    bool mst_on = false;        // the Held-Karp tree bound is built (symmetric matrices only)
+    std::vector<int> seg_buf;         // buffer index (fb) of each segment, bottom first
     std::vector<uint64_t> seg_n;      // paths in each segment
-    PathItem *d_tail = nullptr;
     // one frontier step expands at most min(expand_max, free tail slots / branch)
     // items; bigger steps mean fewer host round trips (n = 30 random, seed 2:
     // 2^23 tails / 2^21 items 2903 steps, 192 ms; 2^26 / 2^24 373 steps, 58 ms;
     // profiles/r02/k2_knobs.log).  Buffers grow on demand.
     unsigned int tail_cap = 1u << 26;
-    unsigned int tail_alloc = 0;
     // 2^21: the output buffer of a step holds T x branch paths, and a step's
     // children can become a segment of their own: at 2^24 a cold 32-city
     // search spent 1.3 s in hipMalloc (1714 vs 524 ms warm), at 2^21 564 vs
     // 545 ms (profiles/r02/k2_expand_cap.log)
-    uint64_t expand_max = (uint64_t)1 << 21;
-    uint64_t expand_steps = 0;  // frontier expansions so far (parity of the double-buffered child counter)  // frontier items one step expands, at most (knob SEARCH_EXPAND_LOG2)
+    uint64_t expand_max = (uint64_t)1 << 21;  // frontier items one step expands, at most (knob SEARCH_EXPAND_LOG2)
+    uint64_t expand_steps = 0;  // frontier expansions so far (parity of the double-buffered child counter)
     uint64_t tails = 0;          // items waiting in d_tail
     int rounds = 0;
     double ms = 0.0;             // device time of all seed/round launches
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    unsigned long long *h_cnt = nullptr;  // pinned host words: the frontier step's counter readback
-    // pinned host copy of the statistics lines + 8 counter words (one DMA
-    // pair and one synchronisation per counters read)
-    unsigned long long *h_stats = nullptr;
-    // device tie rule (search.h): kTieSlots slots, then 8 words: [0..4] the
-    // optimum's slot (tie_lookup_kernel), [5] the overflow flag
-    TieSlot *d_tie = nullptr;
     bool tie_on = true;  // knob SEARCH_TIE=0: records and the host rule only
-    // pinned staging: the host tables of create (so their copies need no
-    // synchronisation) and, at kStageSpec, the speculative records readback
-    char *h_stage = nullptr;
     // search_solve: the chained run enqueues the solve's readbacks (counters,
     // statistics, records, tie slot) before its one synchronisation
     bool fetch = false, fetched = false;
@@ -172,6 +218,8 @@ struct tspgpu_search {
 
 namespace {
 
+using tspgpu::host::falling;
+
 int herr(hipError_t e)
 {
     if (e == hipSuccess) return 0;
@@ -179,138 +227,35 @@ int herr(hipError_t e)
     return -EIO;
 }
 
-uint64_t falling(int N, int D)
-{
-    uint64_t p = 1;
-    for (int l = 0; l < D; ++l) p *= (uint64_t)(N - l);
-    return p;
-}
-
-}  // namespace
-
-// Device buffers a context keeps between searches (hipMalloc of the tail
-// and frontier buffers cost more than a 16-city search itself).  One set per
-// context: the next search takes it, its destroy gives it back.
-namespace {
-struct SearchPool {
-    void *d_dist = nullptr, *d_amin = nullptr;
-    unsigned long long *d_words = nullptr, *d_stats = nullptr;
-    SearchRecord *d_rec = nullptr;
-    unsigned int rec_alloc = 0;
-    SearchItem *d_items[2] = {nullptr, nullptr};
-    size_t item_cap[2] = {0, 0};
-    std::vector<PathItem *> fb;
-    std::vector<size_t> fb_cap;
-    PathItem *d_tail = nullptr;
-    unsigned int tail_alloc = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    unsigned long long *h_cnt = nullptr;
-    unsigned long long *h_stats = nullptr;
-    void *d_bnd2 = nullptr;
-    double *d_mst = nullptr;
-    double *d_hsuf = nullptr;
-    size_t hsuf_alloc = 0;
-    TieSlot *d_tie = nullptr;
-    char *h_stage = nullptr;
-};
-
-template <typename A, typename B>
-void move_buffers(A &to, B &from)
-{
-    to.d_dist = from.d_dist, from.d_dist = nullptr;
-    to.d_amin = from.d_amin, from.d_amin = nullptr;
-    to.d_words = from.d_words, from.d_words = nullptr;
-    to.d_stats = from.d_stats, from.d_stats = nullptr;
-    to.d_rec = from.d_rec, from.d_rec = nullptr;
-    to.rec_alloc = from.rec_alloc, from.rec_alloc = 0;
-    for (int i = 0; i < 2; ++i) {
-        to.d_items[i] = from.d_items[i], from.d_items[i] = nullptr;
-        to.item_cap[i] = from.item_cap[i], from.item_cap[i] = 0;
-    }
-    for (PathItem *p : to.fb)  // (never non-empty at the call sites; freed rather than leaked)
-        if (p) (void)hipFree(p);
-    to.fb = std::move(from.fb);
-    to.fb_cap = std::move(from.fb_cap);
-    from.fb.clear();
-    from.fb_cap.clear();
-    to.d_tail = from.d_tail, from.d_tail = nullptr;
-    to.tail_alloc = from.tail_alloc, from.tail_alloc = 0;
-    to.e0 = from.e0, from.e0 = nullptr;
-    to.e1 = from.e1, from.e1 = nullptr;
-    to.e2 = from.e2, from.e2 = nullptr;
-    to.h_cnt = from.h_cnt, from.h_cnt = nullptr;
-    to.h_stats = from.h_stats, from.h_stats = nullptr;
-    to.d_bnd2 = from.d_bnd2, from.d_bnd2 = nullptr;
-    to.d_mst = from.d_mst, from.d_mst = nullptr;
-    to.d_hsuf = from.d_hsuf, from.d_hsuf = nullptr;
-    to.hsuf_alloc = from.hsuf_alloc, from.hsuf_alloc = 0;
-    to.d_tie = from.d_tie, from.d_tie = nullptr;
-    to.h_stage = from.h_stage, from.h_stage = nullptr;
-}
-
-template <typename A>
-void free_buffers(A &b)
-{
-    if (b.d_dist) (void)hipFree(b.d_dist);
-    if (b.d_amin) (void)hipFree(b.d_amin);
-    if (b.d_words) (void)hipFree(b.d_words);
-    if (b.d_stats) (void)hipFree(b.d_stats);
-    if (b.d_rec) (void)hipFree(b.d_rec);
-    for (int i = 0; i < 2; ++i) {
-        if (b.d_items[i]) (void)hipFree(b.d_items[i]);
-    }
-    for (PathItem *p : b.fb)
-        if (p) (void)hipFree(p);
-    b.fb.clear();
-    b.fb_cap.clear();
-    if (b.d_tail) (void)hipFree(b.d_tail);
-    if (b.e0) (void)hipEventDestroy(b.e0);
-    if (b.e1) (void)hipEventDestroy(b.e1);
-    if (b.e2) (void)hipEventDestroy(b.e2);
-    if (b.h_cnt) (void)hipHostFree(b.h_cnt);
-    if (b.h_stats) (void)hipHostFree(b.h_stats);
-    if (b.d_bnd2) (void)hipFree(b.d_bnd2);
-    if (b.d_mst) (void)hipFree(b.d_mst);
-    if (b.d_hsuf) (void)hipFree(b.d_hsuf);
-    if (b.d_tie) (void)hipFree(b.d_tie);
-    if (b.h_stage) (void)hipHostFree(b.h_stage);
-    SearchPool z;
-    move_buffers(b, z);
-}
-
-void pool_free(void *p)
-{
-    auto *pool = static_cast<SearchPool *>(p);
-    free_buffers(*pool);
-    delete pool;
-}
+void pool_free(void *p) { delete static_cast<SearchBuffers *>(p); }
 
 void take_pool(tspgpu_search *s)
 {
-    SearchPool *pool = nullptr;
+    SearchBuffers *pool = nullptr;
     {
         std::lock_guard<std::mutex> g(s->ctx->mu);
-        pool = static_cast<SearchPool *>(s->ctx->search_pool);
+        pool = static_cast<SearchBuffers *>(s->ctx->search_pool);
         s->ctx->search_pool = nullptr;
     }
     if (!pool) return;
-    move_buffers(*s, *pool);
+    static_cast<SearchBuffers &>(*s) = std::move(*pool);
     delete pool;
 }
 
 void give_pool(tspgpu_search *s)
 {
-    if (s->d_words == nullptr) return;  // a failed create: nothing worth keeping
-    auto *pool = new (std::nothrow) SearchPool();
+    if (!s->d_words) return;  // a failed create: nothing worth keeping
+    auto *pool = new (std::nothrow) SearchBuffers(std::move(static_cast<SearchBuffers &>(*s)));
     if (!pool) return;
-    move_buffers(*pool, *s);
-    std::lock_guard<std::mutex> g(s->ctx->mu);
-    if (!s->ctx->search_pool) {
-        s->ctx->search_pool = pool;
-        s->ctx->search_pool_free = pool_free;
-        pool = nullptr;
+    {
+        std::lock_guard<std::mutex> g(s->ctx->mu);
+        if (!s->ctx->search_pool) {
+            s->ctx->search_pool = pool;
+            s->ctx->search_pool_free = pool_free;
+            pool = nullptr;
+        }
     }
-    if (pool) move_buffers(*s, *pool), delete pool;  // the context has one already: free ours
+    delete pool;  // the context has one already: free ours
 }
 }  // namespace
 
@@ -318,12 +263,148 @@ static void front_release(tspgpu_search *s);
 
 extern "C" {
 
+static bool use_enum_kernel(int n) { return n >= 7 && n <= 16 && tuned_or("ENUM_KERNEL", 1) != 0; }
+
+// tuning knobs (tuning.h; tests and A/B runs only, the members' defaults are the product)
+static void read_knobs(tspgpu_search *s)
+{
+    double kv = 0.0;
+    if (tuned("SEARCH_KERNEL", &kv)) s->opt.kernel = (int)kv == 1 ? 1 : 2;
+    if (tuned("SEARCH_REFILL", &kv) && kv > 0) s->refill = (uint32_t)std::min(kv, 64.0);
+    if (tuned("SEARCH_TAIL", &kv)) s->opt.tail_len = ((int)kv == 5 || (int)kv == 6) ? (int)kv : 0;
+    if (tuned("SEARCH_SUFFIX", &kv)) s->suffix_len = ((int)kv == 5 || (int)kv == 6) ? (int)kv : 0;
+    if (tuned("SEARCH_TWO_EDGE", &kv)) s->opt.use_two_edge = kv != 0;
+    if (tuned("SEARCH_CHAIN", &kv)) s->chain = kv != 0;
+    if (tuned("SEARCH_LAGRANGE", &kv)) s->opt.use_lagrange = kv != 0;
+    if (tuned("SEARCH_MST", &kv)) s->opt.use_mst = kv != 0;
+    if (tuned("SEARCH_MST_MINREM", &kv)) s->opt.mst_min_rem = (int)kv;
+    if (tuned("SEARCH_TAIL_CAP_LOG2", &kv) && kv >= 8 && kv <= 27) s->tail_cap = 1u << (int)kv;  // tests: many flushes
+    if (tuned("SEARCH_EXPAND_LOG2", &kv) && kv >= 8 && kv <= 26) s->expand_max = (uint64_t)1 << (int)kv;
+    if (tuned("SEARCH_BUDGET", &kv) && kv > 0) s->budget = (uint32_t)kv;
+    if (tuned("SEARCH_TIE", &kv)) s->tie_on = kv != 0;
+}
+
+// the buffers the pool did not bring, or brought at another size
+static hipError_t alloc_buffers(tspgpu_search *s)
+{
+    hipError_t e = hipSuccess;
+    if (!s->d_dist) e = dev_alloc(s->d_dist, kSearchMaxN * kSearchMaxN);
+    if (e == hipSuccess && !s->d_amin) e = dev_alloc(s->d_amin, kSearchMaxN);
+    if (e == hipSuccess && !s->d_bnd2) e = dev_alloc(s->d_bnd2, 2 * kSearchMaxN);
+    if (e == hipSuccess && s->mst_on && !s->d_mst) e = dev_alloc(s->d_mst, kSearchMaxN * kSearchMaxN + kSearchMaxN + 1);
+    if (e == hipSuccess && !s->d_words) e = dev_alloc(s->d_words, kWords);
+    if (e == hipSuccess && !s->d_stats) e = dev_alloc(s->d_stats, kStatLines * kStatStride);
+    if (e == hipSuccess && s->frontier && s->d_tail.cap != s->tail_cap) e = dev_alloc(s->d_tail, s->tail_cap);
+    if (e == hipSuccess && s->d_rec.cap < s->rec_cap) e = dev_alloc(s->d_rec, s->rec_cap);
+    // (the 8 trailing words of the tie table: in one more slot's space)
+    static_assert(sizeof(TieSlot) >= 8 * sizeof(unsigned long long), "tie words");
+    if (e == hipSuccess && !s->d_tie) e = dev_alloc(s->d_tie, kTieSlots + 1);
+    if (tuned_or("SEARCH_PAGEABLE", 0) == 0) {
+        if (e == hipSuccess && !s->h_cnt) e = pinned_alloc(s->h_cnt, 16);
+        if (e == hipSuccess && !s->h_stats) e = pinned_alloc(s->h_stats, kStatLines * kStatStride + 8);
+        if (e == hipSuccess && !s->h_stage) e = pinned_alloc(s->h_stage, kStageBytes);
+    }
+    return e;
+}
+
+static hipError_t create_events(tspgpu_search *s)
+{
+    hipError_t e = hipSuccess;
+    for (Event *ev : {&s->e0, &s->e1, &s->e2})
+        if (e == hipSuccess && !*ev) e = hipEventCreate(&ev->p);
+    return e;
+}
+
+static unsigned long long *tie_words(tspgpu_search *s)
+{
+    return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(s->d_tie.p) + kTieBytes);
+}
+
+// the tie slots emptied, the tie words and the statistics zeroed
+static hipError_t reset_tie_stats(tspgpu_search *s)
+{
+    hipStream_t st = s->ctx->stream;
+    hipError_t e = hipMemsetAsync(s->d_tie, 0xFF, kTieBytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(tie_words(s), 0, 8 * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_stats, 0, kStatBytes, st);
+    return e;
+}
+
+// one host table (or the counter words) of create and where it goes
+struct Part {
+    void *dst;
+    const void *src;
+    size_t bytes;
+};
+
+// ONE launch: the tables staged in pinned host memory, read by the kernel
+// directly (no copy commands), the tie slots filled and the statistics zeroed
+// beside them (a dozen memsets and copies took ~70 us of the 16-city search's
+// timeline, profiles/r04).  parts[np - 1] = the counter words w.
+static hipError_t upload_staged(tspgpu_search *s, const Part *parts, int np, const unsigned long long *w,
+                                bool dev_bound, bool symmetric)
+{
+    const int n = s->n;
+    // (the counter words without 1 and 14, the incumbent: block 0 stores those)
+    Part ip[8];
+    int ni = 0;
+    for (int i = 0; i + 1 < np; ++i) ip[ni++] = parts[i];
+    ip[ni++] = {s->d_words, w, 8};
+    ip[ni++] = {s->d_words + 2, w + 2, 12 * 8};
+    ip[ni++] = {s->d_words + 15, w + 15, 8};
+    SearchInit in{};
+    size_t soff = 0;
+    for (int i = 0; i < ni; ++i) {
+        std::memcpy(s->h_stage + soff, ip[i].src, ip[i].bytes);
+        in.src[i] = reinterpret_cast<const uint32_t *>(s->h_stage + soff);
+        in.dst[i] = static_cast<uint32_t *>(ip[i].dst);
+        in.words[i] = (uint32_t)(ip[i].bytes / 4);
+        soff += (ip[i].bytes + 15) & ~(size_t)15;
+    }
+    in.ncopy = ni;
+    in.inc_word[0] = s->d_words + 1;
+    in.inc_word[1] = s->d_words + 14;
+    in.inc_init = w[1];
+    if (dev_bound && n >= 4 && n <= kSearchMaxN) {
+        in.heur_dist = in.src[0];  // (the distances, staged first)
+        in.heur_n = n;
+        in.heur_f64 = s->dtype == TSPGPU_F64 ? 1 : 0;
+        in.heur_sym = symmetric ? 1 : 0;
+        // four spread starts, as the host's (search_host.cpp heuristic): at
+        // 14/16/19 cities the same bound and nodes as 8 or 16 starts, and
+        // each wave has a SIMD to itself (profiles/r04/k2_device_bound.log);
+        // from 20 cities sixteen (the host multi-start takes ~2 ms there)
+        in.heur_starts = n >= 20 ? 16 : 4;
+        in.heur_iters = tuned_int("SEARCH_HEUR_ITERS", 8 * n);
+    }
+    in.fill_ff = reinterpret_cast<uint32_t *>(s->d_tie.p);
+    in.n_ff = (uint32_t)(kTieBytes / 4);
+    in.zero[0] = reinterpret_cast<uint32_t *>(tie_words(s));
+    in.n_zero[0] = 16;
+    in.zero[1] = reinterpret_cast<uint32_t *>(s->d_stats.p);
+    in.n_zero[1] = (uint32_t)(kStatBytes / 4);
+    const hipError_t e = launch_init(in, s->ctx->stream);
+    s->pristine = e == hipSuccess;  // (words 0, 4, 8..13 are zero: the first run skips its memsets)
+    s->dev_heur = e == hipSuccess ? in.heur_n : 0;
+    return e;
+}
+
+// pageable staging (knob SEARCH_PAGEABLE): memsets, copies and a synchronisation
+static hipError_t upload_pageable(tspgpu_search *s, const Part *parts, int np)
+{
+    hipStream_t st = s->ctx->stream;
+    hipError_t e = reset_tie_stats(s);
+    for (int i = 0; i < np && e == hipSuccess; ++i)
+        e = hipMemcpyAsync(parts[i].dst, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+}
+
 // (bound: the initial incumbent, written with the counter words; null: none)
 // (dev_bound: the init launch computes the bound on the device, search.hip
 // init_heuristic; s->dev_heur says whether it did)
 // (enum_shard: an exhaustive shard that will run on the enumeration kernel —
 // it has no frontier, so none of the frontier's buffers is allocated)
-static bool use_enum_kernel(int n) { return n >= 7 && n <= 16 && tuned_or("ENUM_KERNEL", 1) != 0; }
 static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int shard, int nshards, int depth,
                          const double *bound, tspgpu_search **out, bool dev_bound = false, bool enum_shard = false)
 {
@@ -332,7 +413,6 @@ static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int 
     int rc = validate_search(dist, dtype, n);
     if (rc) return rc;
     if (nshards < 1 || shard < 0 || shard >= nshards) return -EINVAL;
-    const int N = n - 1;
     const bool f64 = dtype == TSPGPU_F64;
     if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
     auto *s = new (std::nothrow) tspgpu_search();
@@ -352,207 +432,25 @@ static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int 
     s->dtype = dtype;
     s->shard = (uint32_t)shard;
     s->nshards = (uint32_t)nshards;
-    // tuning knobs (tuning.h; tests and A/B runs only, the defaults above are the product)
-    double kv = 0.0;
-    if (tuned("SEARCH_KERNEL", &kv)) s->kernel = (int)kv == 1 ? 1 : ((int)kv == 3 ? 3 : 2);
-    if (tuned("SEARCH_HUNGRY", &kv)) s->hungry = (int32_t)kv;
-    if (tuned("SEARCH_MIN_SPLIT", &kv)) s->min_split = (uint32_t)std::max(0.0, kv);
-    if (tuned("SEARCH_WALL_S", &kv)) s->wall_s = std::max(0.1, kv);
-    if (tuned("SEARCH_RING_LOG2", &kv) && kv >= 6 && kv <= 24) s->ring_cap = 1u << (int)kv;  // tests: a small ring
-    if (tuned("SEARCH_REFILL", &kv) && kv > 0) s->refill = (uint32_t)std::min(kv, 64.0);
-    if (tuned("SEARCH_TAIL", &kv)) s->tail_len = ((int)kv == 5 || (int)kv == 6) ? (int)kv : 0;
-    if (tuned("SEARCH_SUFFIX", &kv)) s->suffix_len = ((int)kv == 5 || (int)kv == 6) ? (int)kv : 0;
-    if (tuned("SEARCH_TWO_EDGE", &kv)) s->use_two_edge = kv != 0;
-    if (tuned("SEARCH_CHAIN", &kv)) s->chain = kv != 0;
-    if (tuned("SEARCH_LAGRANGE", &kv)) s->use_lagrange = kv != 0;
-    if (tuned("SEARCH_MST", &kv)) s->use_mst = kv != 0;
-    if (tuned("SEARCH_MST_MINREM", &kv)) s->mst_min_rem = (int)kv;
-    if (tuned("SEARCH_TAIL_CAP_LOG2", &kv) && kv >= 8 && kv <= 27) s->tail_cap = 1u << (int)kv;  // tests: many flushes
-    if (tuned("SEARCH_EXPAND_LOG2", &kv) && kv >= 8 && kv <= 26) s->expand_max = (uint64_t)1 << (int)kv;
-    const size_t lds = search_lds_bytes(n, f64, s->kernel == 1 ? 1 : 2);
+    read_knobs(s);
+    const size_t lds = search_lds_bytes(n, f64, s->opt.kernel);
     const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / lds)));
     s->grid = c->cu_count * per_cu;
-    // seed depth: the smallest D with at least one prefix per lane of the
-    // whole grid (the rounds split whatever is still too coarse), at most
-    // N-1, at least 1, and < 2^31 prefixes
-    const uint64_t lanes = (uint64_t)s->grid * kSearchThreads * (uint64_t)nshards;
-    const bool auto_depth = depth <= 0;
-    if (depth <= 0) {
-        depth = 1;
-        while (depth < N - 1 && falling(N, depth + 1) < (1ull << 31) && falling(N, depth) < lanes) ++depth;
-    }
-    if (depth > N - 1) depth = N - 1;
-    while (depth > 1 && falling(N, depth) >= (1ull << 31)) --depth;
-    if (tuned("SEARCH_BUDGET", &kv) && kv > 0) s->budget = (uint32_t)kv;
-    s->frontier = s->tail_len && s->kernel == 2 && N - s->tail_len > depth && !enum_shard;
-    // the frontier search expands level by level with its own bounds: a
-    // smaller seed set (~64 prefixes per CU) costs less than the round
-    // kernels' one-per-lane (measured at n = 16: depth 4 vs 5, 0.14 vs 0.16 ms)
-    if (s->frontier && auto_depth) {
-        const uint64_t want = (uint64_t)c->cu_count * 64 * nshards;
-        int d = 1;
-        while (d < depth && falling(N, d) < want) ++d;
-        // several shards: one level deeper, so that the heavy subtrees near
-        // the optimum spread over the shards (n = 30 random, 8 shards: node
-        // imbalance max/mean 1.91 at depth 4, 1.20 at depth 5;
-        // profiles/r02/k2_shard_balance_depth.log)
-        // Not with the tree bound (symmetric matrices): it leaves no heavy
-        // subtree to spread, and the deeper seed level, bounded only by B0/B1,
-        // costs more than it balances (n = 32 seed 35, 2 shards: 5.0e7 nodes
-        // per shard vs 7.1e5 for one GPU; profiles/r02/k2_shard_depth_tree.log)
-        bool tree = s->use_mst && s->use_two_edge;
-        for (int i = 0; i < n && tree; ++i)
-            for (int j = 0; j < i && tree; ++j)
-                tree = f64 ? static_cast<const double *>(dist)[i * n + j] == static_cast<const double *>(dist)[j * n + i]
-                           : static_cast<const int32_t *>(dist)[i * n + j] == static_cast<const int32_t *>(dist)[j * n + i];
-        if (nshards > 1 && !tree && d + 1 < N - s->tail_len && falling(N, d + 1) < (1ull << 31)) ++d;
-        depth = d;
-    }
-    s->depth = depth;
-    s->items = falling(N, depth);
-    s->local_items = s->items / nshards + (s->items % nshards > (uint64_t)shard ? 1 : 0);
-    const size_t vb = f64 ? sizeof(double) : sizeof(int32_t);
-    // cheapest incoming edge per city; f64 rounded DOWN to a 2^-20 grid
-    std::vector<double> ad(n);
-    std::vector<int32_t> ai(n);
-    if (f64) {
-        const double *d = static_cast<const double *>(dist);
-        s->hd.assign(d, d + n * n);
-        for (int x = 0; x < n; ++x) {
-            double m = INFINITY;
-            for (int i = 0; i < n; ++i)
-                if (i != x) m = std::min(m, d[i * n + x]);
-            ad[x] = std::ldexp(std::floor(std::ldexp(m, 20)), -20);
-        }
-    } else {
-        const int32_t *d = static_cast<const int32_t *>(dist);
-        s->hi.assign(d, d + n * n);
-        for (int x = 0; x < n; ++x) {
-            int32_t m = INT32_MAX;
-            for (int i = 0; i < n; ++i)
-                if (i != x) m = std::min(m, d[i * n + x]);
-            ai[x] = m;
-        }
-    }
-    // two-edge bound (symmetric matrices): per city x, b[x] = half the sum of
-    // its two cheapest incident edges, e[x] = half its cheapest, rounded down
-    // to the bound's grid (f64: 2^-20, exact sums; i32: integers)
-    std::vector<double> bd(2 * n, 0.0);
-    std::vector<int32_t> bi(2 * n, 0);
-    std::vector<double> hk_pi;  // Held-Karp weights of the tree bound (symmetric matrices)
-    {
-        bool sym = s->use_two_edge;
-        for (int i = 0; i < n && sym; ++i)
-            for (int j = 0; j < i && sym; ++j)
-                sym = f64 ? static_cast<const double *>(dist)[i * n + j] == static_cast<const double *>(dist)[j * n + i]
-                          : static_cast<const int32_t *>(dist)[i * n + j] == static_cast<const int32_t *>(dist)[j * n + i];
-        s->sym = sym ? 1 : 0;
-        if (sym) {
-            std::vector<double> D((size_t)n * n);
-            for (int i = 0; i < n * n; ++i)
-                D[i] = f64 ? static_cast<const double *>(dist)[i] : (double)static_cast<const int32_t *>(dist)[i];
-            std::vector<double> pi(n, 0.0);
-            // the tree bound's weights on a second thread meanwhile (host time
-            // at n = 32: 1.3 ms beside lagrange_pi's 0.45 ms)
-            // (only if some path can reach it: the expand kernel applies the
-            // tree bound to paths with >= mst_min_rem cities left, and the
-            // frontier starts at the seed depth — at n = 16 none does, and
-            // the weights cost 0.22 ms of host time, profiles/r03/k2_variants.log)
-            const bool want_tree = s->use_mst && n >= 4 && s->frontier && N - depth >= s->mst_min_rem;
-            std::thread ht;
-            bool threaded = false;
-            if (want_tree && n >= 20) {  // (smaller: a thread costs more than it saves)
-                try {
-                    ht = std::thread([&] { held_karp_pi(D, n, hk_pi); });
-                    threaded = true;
-                } catch (...) {
-                }
-            }
-            if (s->use_lagrange) lagrange_pi(D, n, pi);
-            if (threaded)
-                ht.join();
-            else if (want_tree)
-                held_karp_pi(D, n, hk_pi);
-            for (int x = 0; x < n; ++x) {
-                double m1 = INFINITY, m2 = INFINITY;  // the two cheapest d'[x][y] = d + pi_x + pi_y
-                for (int y = 0; y < n; ++y) {
-                    if (y == x) continue;
-                    const double v = D[(size_t)x * n + y] + pi[x] + pi[y];
-                    if (v < m1) {
-                        m2 = m1;
-                        m1 = v;
-                    } else if (v < m2) {
-                        m2 = v;
-                    }
-                }
-                // b = (m1 + m2)/2 - 2 pi_x, e = m1/2 - pi_x: lower bounds, so
-                // a margin for the double rounding of d + pi + pi, then DOWN
-                // to the grid
-                const double bx = (m1 + m2) * 0.5 - 2.0 * pi[x], ex = m1 * 0.5 - pi[x];
-                const double mg = 1e-9 * (std::fabs(m1) + std::fabs(m2) + 4.0 * std::fabs(pi[x]) + 1.0);
-                if (f64) {
-                    bd[2 * x] = std::ldexp(std::floor(std::ldexp(bx - mg, 20)), -20);
-                    bd[2 * x + 1] = std::ldexp(std::floor(std::ldexp(ex - mg, 20)), -20);
-                } else {
-                    bi[2 * x] = (int32_t)std::floor(bx - mg);
-                    bi[2 * x + 1] = (int32_t)std::floor(ex - mg);
-                }
-            }
-        }
-    }
-    // tree bound (symmetric matrices): d' and pi as doubles, and a margin far
-    // above the rounding of the device's sums of <= 2n + 2 such terms
-    std::vector<double> mt;
-    s->mst_on = s->sym && s->use_mst && !s->noprune && n >= 4 && (int)hk_pi.size() == n;
-    if (s->mst_on) {
-        std::vector<double> D((size_t)n * n);
-        const std::vector<double> &pi = hk_pi;
-        for (int i = 0; i < n * n; ++i)
-            D[i] = f64 ? static_cast<const double *>(dist)[i] : (double)static_cast<const int32_t *>(dist)[i];
-        mt.assign((size_t)n * n + n + 1, 0.0);
-        double mx = 0.0, ps = 0.0;
-        for (int x = 0; x < n; ++x)
-            for (int y = 0; y < n; ++y) {
-                mt[(size_t)x * n + y] = D[(size_t)x * n + y] + pi[x] + pi[y];
-                mx = std::max(mx, std::fabs(mt[(size_t)x * n + y]));
-            }
-        for (int x = 0; x < n; ++x) mt[(size_t)n * n + x] = pi[x], ps += std::fabs(pi[x]);
-        mt[(size_t)n * n + n] = 1e-9 * ((n + 2) * mx + 2.0 * ps + 1.0);
-    }
+    // the host plan (search_host.cpp): seed depth, then the bound tables
+    const bool symmetric = tspgpu::host::is_symmetric(dist, dtype, n);
+    const tspgpu::host::SeedPlan plan = tspgpu::host::plan_seeds(
+        n, shard, nshards, depth, (uint64_t)s->grid * kSearchThreads, c->cu_count, s->opt, symmetric, enum_shard);
+    s->depth = plan.depth;
+    s->items = plan.items;
+    s->local_items = plan.local_items;
+    s->frontier = plan.frontier;
+    tspgpu::host::BoundTables tab;
+    tspgpu::host::build_bound_tables(dist, dtype, n, symmetric, plan, s->opt, tab);
+    s->sym = tab.sym;
+    s->mst_on = tab.mst_on;
     s->rec_cap = 1u << 16;
     take_pool(s);  // device buffers of the context's previous search, if any
-    hipStream_t st = c->stream;
-    hipError_t e = hipSuccess;
-    if (!s->d_dist) e = hipMalloc(&s->d_dist, sizeof(double) * kSearchMaxN * kSearchMaxN);
-    if (e == hipSuccess && !s->d_amin) e = hipMalloc(&s->d_amin, sizeof(double) * kSearchMaxN);
-    if (e == hipSuccess && !s->d_bnd2) e = hipMalloc(&s->d_bnd2, sizeof(double) * 2 * kSearchMaxN);
-    if (e == hipSuccess && s->mst_on && !s->d_mst)
-        e = hipMalloc((void **)&s->d_mst, sizeof(double) * (kSearchMaxN * kSearchMaxN + kSearchMaxN + 1));
-    if (e == hipSuccess && !s->d_words) e = hipMalloc((void **)&s->d_words, kWords * sizeof(unsigned long long));
-    if (e == hipSuccess && !s->d_stats) e = hipMalloc((void **)&s->d_stats, kStatBytes);
-    if (e == hipSuccess && s->frontier && s->d_tail && s->tail_alloc != s->tail_cap) {
-        (void)hipFree(s->d_tail);
-        s->d_tail = nullptr;
-    }
-    if (e == hipSuccess && s->frontier && !s->d_tail) {
-        e = hipMalloc((void **)&s->d_tail, sizeof(PathItem) * s->tail_cap);
-        if (e == hipSuccess) s->tail_alloc = s->tail_cap;
-    }
-    if (e == hipSuccess && s->rec_alloc < s->rec_cap) {
-        if (s->d_rec) (void)hipFree(s->d_rec);
-        s->d_rec = nullptr;
-        e = hipMalloc((void **)&s->d_rec, sizeof(SearchRecord) * s->rec_cap);
-        if (e == hipSuccess) s->rec_alloc = s->rec_cap;
-    }
-    if (double v; tuned("SEARCH_TIE", &v)) s->tie_on = v != 0;
-    constexpr size_t kTieBytes = sizeof(TieSlot) * kTieSlots;
-    if (e == hipSuccess && !s->d_tie) e = hipMalloc((void **)&s->d_tie, kTieBytes + 8 * sizeof(unsigned long long));
-    const bool pinned = tuned_or("SEARCH_PAGEABLE", 0) == 0;
-    if (e == hipSuccess && pinned && !s->h_cnt)
-        e = hipHostMalloc((void **)&s->h_cnt, 16 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess && pinned && !s->h_stats)
-        e = hipHostMalloc((void **)&s->h_stats, kStatBytes + 8 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess && pinned && !s->h_stage) e = hipHostMalloc((void **)&s->h_stage, kStageBytes, hipHostMallocDefault);
+    hipError_t e = alloc_buffers(s);
     unsigned long long w[kWords] = {};
     if (f64) {
         const double inf = INFINITY;
@@ -562,84 +460,21 @@ static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int 
     }
     w[14] = w[1];  // the incumbent a chain starts from (run_chain copies it only after a run)
     // the host tables and the counter words, with the sizes
-    struct Part {
-        void *dst;
-        const void *src;
-        size_t bytes;
-    };
+    const size_t vb = f64 ? sizeof(double) : sizeof(int32_t);
     Part parts[5];
     int np = 0;
     parts[np++] = {s->d_dist, dist, vb * n * n};
-    parts[np++] = {s->d_amin, f64 ? (const void *)ad.data() : (const void *)ai.data(), vb * n};
-    if (s->sym) parts[np++] = {s->d_bnd2, f64 ? (const void *)bd.data() : (const void *)bi.data(), vb * 2 * n};
-    if (s->mst_on) parts[np++] = {s->d_mst, mt.data(), sizeof(double) * mt.size()};
+    parts[np++] = {s->d_amin, f64 ? (const void *)tab.amin_d.data() : (const void *)tab.amin_i.data(), vb * n};
+    if (s->sym)
+        parts[np++] = {s->d_bnd2, f64 ? (const void *)tab.bnd2_d.data() : (const void *)tab.bnd2_i.data(), vb * 2 * n};
+    if (s->mst_on) parts[np++] = {s->d_mst, tab.mt.data(), sizeof(double) * tab.mt.size()};
     parts[np++] = {s->d_words, w, sizeof w};
     size_t need = 0;
     for (int i = 0; i < np; ++i) need += (parts[i].bytes + 15) & ~(size_t)15;
-    if (e == hipSuccess && s->h_stage && need <= kStageSpec) {
-        // ONE launch: the tables staged in pinned host memory, read by the
-        // kernel directly (no copy commands), the tie slots filled and the
-        // statistics zeroed beside them (a dozen memsets and copies took
-        // ~70 us of the 16-city search's timeline, profiles/r04)
-        // (the counter words without 1 and 14, the incumbent: block 0 stores those)
-        Part ip[8];
-        int ni = 0;
-        for (int i = 0; i + 1 < np; ++i) ip[ni++] = parts[i];
-        ip[ni++] = {s->d_words, w, 8};
-        ip[ni++] = {s->d_words + 2, w + 2, 12 * 8};
-        ip[ni++] = {s->d_words + 15, w + 15, 8};
-        SearchInit in{};
-        size_t soff = 0;
-        for (int i = 0; i < ni; ++i) {
-            std::memcpy(s->h_stage + soff, ip[i].src, ip[i].bytes);
-            in.src[i] = reinterpret_cast<const uint32_t *>(s->h_stage + soff);
-            in.dst[i] = static_cast<uint32_t *>(ip[i].dst);
-            in.words[i] = (uint32_t)(ip[i].bytes / 4);
-            soff += (ip[i].bytes + 15) & ~(size_t)15;
-        }
-        in.ncopy = ni;
-        in.inc_word[0] = s->d_words + 1;
-        in.inc_word[1] = s->d_words + 14;
-        in.inc_init = w[1];
-        if (dev_bound && n >= 4 && n <= kSearchMaxN) {
-            bool msym = true;
-            for (int i = 0; i < n && msym; ++i)
-                for (int j = 0; j < i && msym; ++j)
-                    msym = f64 ? static_cast<const double *>(dist)[i * n + j] == static_cast<const double *>(dist)[j * n + i]
-                               : static_cast<const int32_t *>(dist)[i * n + j] == static_cast<const int32_t *>(dist)[j * n + i];
-            in.heur_dist = in.src[0];  // (the distances, staged first)
-            in.heur_n = n;
-            in.heur_f64 = f64 ? 1 : 0;
-            in.heur_sym = msym ? 1 : 0;
-            // four spread starts, as the host's (search_host.cpp heuristic): at
-            // 14/16/19 cities the same bound and nodes as 8 or 16 starts, and
-            // each wave has a SIMD to itself (profiles/r04/k2_device_bound.log);
-            // from 20 cities sixteen (the host multi-start takes ~2 ms there)
-            in.heur_starts = n >= 20 ? 16 : 4;
-            in.heur_iters = tuned_int("SEARCH_HEUR_ITERS", 8 * n);
-        }
-        in.fill_ff = reinterpret_cast<uint32_t *>(s->d_tie);
-        in.n_ff = (uint32_t)(kTieBytes / 4);
-        in.zero[0] = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s->d_tie) + kTieBytes);
-        in.n_zero[0] = 16;
-        in.zero[1] = reinterpret_cast<uint32_t *>(s->d_stats);
-        in.n_zero[1] = (uint32_t)(kStatBytes / 4);
-        e = launch_init(in, st);
-        s->pristine = e == hipSuccess;  // (words 0, 4, 8..13 are zero: the first run skips its memsets)
-        s->dev_heur = e == hipSuccess ? in.heur_n : 0;
-    } else if (e == hipSuccess) {
-        // pageable staging (knob SEARCH_PAGEABLE): memsets, copies and a synchronisation
-        e = hipMemsetAsync(s->d_tie, 0xFF, kTieBytes, st);
-        if (e == hipSuccess)
-            e = hipMemsetAsync(reinterpret_cast<char *>(s->d_tie) + kTieBytes, 0, 8 * sizeof(unsigned long long), st);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_stats, 0, kStatBytes, st);
-        for (int i = 0; i < np && e == hipSuccess; ++i)
-            e = hipMemcpyAsync(parts[i].dst, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (e == hipSuccess && !s->e0) e = hipEventCreate(&s->e0);
-    if (e == hipSuccess && !s->e1) e = hipEventCreate(&s->e1);
-    if (e == hipSuccess && !s->e2) e = hipEventCreate(&s->e2);
+    if (e == hipSuccess)
+        e = s->h_stage && need <= kStageSpec ? upload_staged(s, parts, np, w, dev_bound, symmetric)
+                                             : upload_pageable(s, parts, np);
+    if (e == hipSuccess) e = create_events(s);
     if (e != hipSuccess) {
         tspgpu_search_destroy(s);
         return herr(e);
@@ -675,7 +510,7 @@ static void set_mode(tspgpu_search *s, bool exhaustive)
         const int N = n - 1, G = N - 6;
         s->depth = G;
         s->items = falling(N, G);  // <= 15!/6! < 2^31
-        s->local_items = s->items / s->nshards + (s->items % s->nshards > (uint64_t)s->shard ? 1 : 0);
+        s->local_items = tspgpu::host::shard_items(s->items, s->shard, s->nshards);
         s->frontier = false;
     }
 }
@@ -713,11 +548,8 @@ int tspgpu_search_destroy(tspgpu_search *s)
     (void)hipStreamSynchronize(s->ctx->stream);
     front_release(s);
     give_pool(s);  // the buffers stay with the context for its next search
-    free_buffers(*s);
-    if (s->d_ps) (void)hipFree(s->d_ps);
-    if (s->d_ring) (void)hipFree(s->d_ring);
     tspgpu_ctx *c = s->ctx;
-    delete s;
+    delete s;  // (frees whatever the pool did not take)
     // dropping the reference is the last use of the context: when
     // tspgpu_ctx_destroy came first, the last search releases it (with the
     // pool just given back)
@@ -760,11 +592,6 @@ int tspgpu_search_set_bound(tspgpu_search *s, double bound)
     return herr(e);
 }
 
-static unsigned long long *tie_words(tspgpu_search *s)
-{
-    return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(s->d_tie) + sizeof(TieSlot) * kTieSlots);
-}
-
 static SearchArgs args_of(tspgpu_search *s)
 {
     SearchArgs a{};
@@ -777,19 +604,19 @@ static SearchArgs args_of(tspgpu_search *s)
     a.nshards = s->nshards;
     a.budget = s->budget;
     a.refill = s->refill;
-    a.kernel = s->kernel == 1 && !s->noprune ? 1 : 2;  // the round kernels (2 for enumeration)
+    a.kernel = s->opt.kernel == 1 && !s->noprune ? 1 : 2;  // the round kernels (2 for enumeration)
     a.noprune = s->noprune;
     a.tails = s->noprune;  // knob SEARCH_TAILS=0/1 overrides
     if (double v; tuned("SEARCH_TAILS", &v)) a.tails = v != 0;
-    a.queue = reinterpret_cast<unsigned int *>(s->d_words);
+    a.queue = reinterpret_cast<unsigned int *>(s->d_words.p);
     a.inc = s->d_words + 1;
     a.nodes = s->d_stats;
     a.rec_count = reinterpret_cast<unsigned int *>(s->d_words + 3);
     a.out_count = reinterpret_cast<unsigned int *>(s->d_words + 4);
     a.tail_count = reinterpret_cast<unsigned int *>(s->d_words + 8);
     if (s->frontier) {
-        a.tail_len = s->tail_len;
-        a.tail_level = s->n - 1 - s->tail_len;
+        a.tail_len = s->opt.tail_len;
+        a.tail_level = s->n - 1 - s->opt.tail_len;
         a.ftail = s->d_tail;
         a.tail_cap = s->tail_cap;
     }
@@ -798,7 +625,7 @@ static SearchArgs args_of(tspgpu_search *s)
     a.bnd2 = s->d_bnd2;
     a.sym = s->sym;
     a.mst = s->mst_on ? s->d_mst : nullptr;
-    a.mst_min_rem = s->mst_min_rem;
+    a.mst_min_rem = s->opt.mst_min_rem;
     a.hsuf = s->d_hsuf;
     a.hs_len = s->hs_len;
     for (int i = 0; i < 8; ++i) a.hs_off[i] = s->hs_off[i];
@@ -829,17 +656,11 @@ static double wall_clock_khz(int device)
 
 static int ensure_items(tspgpu_search *s, int which, size_t count)
 {
-    if (s->item_cap[which] >= count && s->d_items[which]) return 0;
+    if (s->d_items[which].cap >= count) return 0;
     // grow geometrically (up to 2^27 items) so that rounds rarely reallocate
     const size_t cap = std::max<size_t>(std::max<size_t>(count, 1024),
-                                        std::min<size_t>(2 * s->item_cap[which], (size_t)1 << 27));
-    if (s->d_items[which]) (void)hipFree(s->d_items[which]);
-    s->d_items[which] = nullptr;
-    s->item_cap[which] = 0;
-    hipError_t e = hipMalloc((void **)&s->d_items[which], cap * sizeof(SearchItem));
-    if (e != hipSuccess) return herr(e);
-    s->item_cap[which] = cap;
-    return 0;
+                                        std::min<size_t>(2 * s->d_items[which].cap, (size_t)1 << 27));
+    return herr(dev_alloc(s->d_items[which], cap));
 }
 
 // the statistics lines, summed: [0] nodes, [1] lane slots, [2] active lane steps, [3] item loads
@@ -876,20 +697,18 @@ static int front_spare(tspgpu_search *s, size_t count, int *rc)
     for (int i = 0; i < (int)s->fb.size(); ++i) {
         bool used = false;
         for (int b : s->seg_buf) used = used || b == i;
-        if (used || !s->fb[i] || s->fb_cap[i] < count) continue;
-        if (best < 0 || s->fb_cap[i] < s->fb_cap[best]) best = i;
+        if (used || s->fb[i].cap < count) continue;
+        if (best < 0 || s->fb[i].cap < s->fb[best].cap) best = i;
     }
     if (best >= 0) return best;
     const size_t gran = (size_t)1 << 20;
     const size_t cap = std::max<size_t>(4096, count <= 4096 ? 4096 : (count + gran - 1) / gran * gran);
-    PathItem *p = nullptr;
-    hipError_t e = hipMalloc((void **)&p, cap * sizeof(PathItem));
-    if (e != hipSuccess) {
+    DevBuf<PathItem> b;
+    if (hipError_t e = dev_alloc(b, cap); e != hipSuccess) {
         *rc = herr(e);
         return -1;
     }
-    s->fb.push_back(p);
-    s->fb_cap.push_back(cap);
+    s->fb.push_back(std::move(b));
     return (int)s->fb.size() - 1;
 }
 
@@ -900,6 +719,18 @@ static void front_release(tspgpu_search *s)
     s->seg_n.clear();
 }
 
+// the queue (word 0) and the items-out count (word 4) zeroed, unless create's launch just did
+static hipError_t zero_queue(tspgpu_search *s)
+{
+    hipError_t e = hipSuccess;
+    if (!s->pristine) {
+        e = hipMemsetAsync(s->d_words, 0, 8, s->ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(s->d_words + 4, 0, 8, s->ctx->stream);
+    }
+    s->pristine = false;
+    return e;
+}
+
 // launch + wait + read the item count the launch produced (sync = false: the
 // count stays in word 4 for a chained search to read on the device; the
 // launch's time is then the chain's)
@@ -907,12 +738,7 @@ static int launch_and_count(tspgpu_search *s, bool seed, int grid, SearchArgs &a
                             bool sync = true)
 {
     hipStream_t st = s->ctx->stream;
-    hipError_t e = hipSuccess;
-    if (!s->pristine) {
-        e = hipMemsetAsync(s->d_words, 0, 8, st);  // queue
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_words + 4, 0, 8, st);  // items out
-    }
-    s->pristine = false;
+    hipError_t e = zero_queue(s);
     if (e != hipSuccess) return herr(e);
     if (sync) (void)hipEventRecord(s->e0, st);  // (a chain times itself: SearchArgs::t_start)
     if (seed && suffix_sets)  // the frontier's seeds and its suffix table, side by side in one launch
@@ -941,20 +767,13 @@ static int build_suffix(tspgpu_search *s, bool launch, uint32_t *sets_out)
     *sets_out = 0;
     // the frontier's expansion tests children with tail_len cities left: the
     // table has that size there; the lock-step DFS tests at suffix_len
-    const int N = s->n - 1, L = s->frontier ? s->tail_len : s->suffix_len;
-    if (s->noprune || s->suffix_len == 0 || L < 1 || N < L + 2 || s->kernel == 1 || s->kernel == 3) return 0;
+    const int N = s->n - 1, L = s->frontier ? s->opt.tail_len : s->suffix_len;
+    if (s->noprune || s->suffix_len == 0 || L < 1 || N < L + 2 || s->opt.kernel == 1) return 0;
     for (int k = 0; k < 8; ++k) s->hs_off[k] = 0;  // one size stored: L, at offset 0
     const uint32_t sets = search_binom(N, L), off = sets * (uint32_t)L;
-    const size_t bytes = (size_t)off * sizeof(double);
     hipStream_t st = s->ctx->stream;
-    if (s->hsuf_alloc < bytes) {
-        if (s->d_hsuf) (void)hipFree(s->d_hsuf);
-        s->d_hsuf = nullptr;
-        s->hsuf_alloc = 0;
-        hipError_t e = hipMalloc((void **)&s->d_hsuf, bytes);
-        if (e != hipSuccess) return herr(e);
-        s->hsuf_alloc = bytes;
-    }
+    if (s->d_hsuf.cap < off)
+        if (hipError_t e = dev_alloc(s->d_hsuf, off); e != hipSuccess) return herr(e);
     s->hs_len = L;
     *sets_out = sets;
     if (!launch) return 0;  // the caller launches it (with the seeds)
@@ -979,27 +798,52 @@ int tspgpu_search_start(tspgpu_search *s)
     return search_start(s, true);
 }
 
+// What every start begins with: the item buffer, the round state reset and,
+// for the frontier, the tails (word 8) and the odd steps' child counter (word 9) zeroed
+static int begin_start(tspgpu_search *s)
+{
+    (void)hipSetDevice(s->ctx->device);
+    s->fresh = false;
+    if (int rc = ensure_items(s, 0, s->local_items + 1)) return rc;
+    s->cur = 0;
+    s->rounds = 0;
+    s->tails = 0;
+    if (s->frontier) {
+        hipError_t e = s->pristine ? hipSuccess : hipMemsetAsync(s->d_words + 8, 0, 16, s->ctx->stream);
+        if (e != hipSuccess) return herr(e);
+        s->expand_steps = 0;
+    }
+    return 0;
+}
+
+// the seed launch's grid: a lane per prefix of this shard, at most 8 blocks per CU
+static int seed_grid(const tspgpu_search *s)
+{
+    const uint64_t blocks = (s->local_items + kSearchThreads - 1) / kSearchThreads;
+    return (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)s->ctx->cu_count * 8));
+}
+
+// knob SEARCH_CHAIN_POISON (tests): the chain's level buffers and the tail
+// buffer filled with 0xFF first — no slot may be read that was not written
+static hipError_t poison_chain(tspgpu_search *s, const int ob[2], uint64_t cap)
+{
+    if (tuned_or("SEARCH_CHAIN_POISON", 0) == 0) return hipSuccess;
+    hipStream_t st = s->ctx->stream;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMemsetAsync(s->fb[ob[k]], 0xFF, sizeof(PathItem) * cap, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_tail, 0xFF, sizeof(PathItem) * s->tail_cap, st);
+    return e;
+}
+
 // sync = false (chained searches): the seeds' launch is only enqueued, their
 // count stays on the device (word 4), s->pending is the upper bound
 // local_items and the seed segment is left to the caller
 static int search_start(tspgpu_search *s, bool sync)
 {
-    (void)hipSetDevice(s->ctx->device);
-    s->fresh = false;
-    if (int rc = ensure_items(s, 0, s->local_items + 1)) return rc;
-    SearchArgs a = args_of(s);
-    a.out = s->d_items[0];
-    s->cur = 0;
-    s->rounds = 0;
-    s->tails = 0;
-    if (s->frontier) {  // tails (word 8) and the odd steps' child counter (word 9)
-        hipError_t e = s->pristine ? hipSuccess : hipMemsetAsync(s->d_words + 8, 0, 16, s->ctx->stream);
-        if (e != hipSuccess) return herr(e);
-        s->expand_steps = 0;
-    }
+    if (int rc = begin_start(s)) return rc;
     uint32_t sets = 0;  // the frontier builds its suffix table in the seed launch
     if (int rc = build_suffix(s, !s->frontier, &sets)) return rc;
-    a = args_of(s);
+    SearchArgs a = args_of(s);
     a.out = s->d_items[0];
     int seed_buf = -1;
     if (s->frontier) {  // the live seeds are written as the first frontier segment (32-byte paths)
@@ -1010,9 +854,7 @@ static int search_start(tspgpu_search *s, bool sync)
         if (seed_buf < 0) return rc;
         a.fout = s->fb[seed_buf];
     }
-    const uint64_t blocks = (s->local_items + kSearchThreads - 1) / kSearchThreads;
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)s->ctx->cu_count * 8));
-    int rc = launch_and_count(s, true, grid, a, s->frontier ? sets : 0u, sync);
+    int rc = launch_and_count(s, true, seed_grid(s), a, s->frontier ? sets : 0u, sync);
     if (!rc && !sync) {
         s->pending = s->local_items;
         s->seg_buf.push_back(seed_buf);
@@ -1034,22 +876,12 @@ static int search_start(tspgpu_search *s, bool sync)
 static bool fusable(const tspgpu_search *s)
 {
     // build_suffix's conditions for a frontier table, and a size prologue1 has
-    const int N = s->n - 1, L = s->tail_len;
-    return s->frontier && !s->noprune && s->suffix_len != 0 && (L == 5 || L == 6) && N >= L + 2 && s->kernel != 1 &&
-           s->kernel != 3;
+    const int N = s->n - 1, L = s->opt.tail_len;
+    return s->frontier && !s->noprune && s->suffix_len != 0 && (L == 5 || L == 6) && N >= L + 2 && s->opt.kernel != 1;
 }
 static int search_start_fused(tspgpu_search *s, uint64_t cap, int ob[2])
 {
-    (void)hipSetDevice(s->ctx->device);
-    s->fresh = false;
-    if (int rc = ensure_items(s, 0, s->local_items + 1)) return rc;
-    s->cur = 0;
-    s->rounds = 0;
-    s->tails = 0;
-    hipStream_t st = s->ctx->stream;
-    hipError_t e = s->pristine ? hipSuccess : hipMemsetAsync(s->d_words + 8, 0, 16, st);
-    if (e != hipSuccess) return herr(e);
-    s->expand_steps = 0;
+    if (int rc = begin_start(s)) return rc;  // (fusable: a frontier search)
     uint32_t sets = 0;
     if (int rc = build_suffix(s, false, &sets)) return rc;
     if (!sets) return -EIO;  // (run_chain fuses only when the table is built: fusable())
@@ -1066,25 +898,15 @@ static int search_start_fused(tspgpu_search *s, uint64_t cap, int ob[2])
         s->seg_buf.push_back(ob[k]);  // (marked used so the second front_spare picks another)
         s->seg_n.push_back(0);
     }
-    if (tuned_or("SEARCH_CHAIN_POISON", 0) != 0) {  // tests: no slot may be read that was not written
-        for (int k = 0; k < 2 && e == hipSuccess; ++k)
-            e = hipMemsetAsync(s->fb[ob[k]], 0xFF, sizeof(PathItem) * cap, st);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_tail, 0xFF, sizeof(PathItem) * s->tail_cap, st);
-    }
-    if (!s->pristine && e == hipSuccess) {
-        e = hipMemsetAsync(s->d_words, 0, 8, st);  // queue
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_words + 4, 0, 8, st);  // items out
-    }
-    s->pristine = false;
+    hipError_t e = poison_chain(s, ob, cap);
+    if (e == hipSuccess) e = zero_queue(s);
     if (e != hipSuccess) return herr(e);
     SearchArgs a = args_of(s);
     a.fout = s->fb[ob[0]];
     a.fout_cap = (uint32_t)cap;
     a.out_count = reinterpret_cast<unsigned int *>(s->d_words + 11);
     a.overflow = reinterpret_cast<unsigned int *>(s->d_words + 13);
-    const uint64_t blocks = (s->local_items + kSearchThreads - 1) / kSearchThreads;
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)s->ctx->cu_count * 8));
-    e = launch_prologue1(a, s->dtype == TSPGPU_F64, grid, sets);
+    e = launch_prologue1(a, s->dtype == TSPGPU_F64, seed_grid(s), sets);
     if (e != hipSuccess) return herr(e);
     s->pending = s->local_items;
     return 0;
@@ -1172,7 +994,7 @@ static int frontier_step(tspgpu_search *s, uint64_t *pending)
         s->seg_n.pop_back();
     }
     constexpr uint64_t kAppendMax = (uint64_t)1 << 20;
-    if (kids && !s->seg_n.empty() && kids <= kAppendMax && s->fb_cap[s->seg_buf.back()] >= s->seg_n.back() + kids) {
+    if (kids && !s->seg_n.empty() && kids <= kAppendMax && s->fb[s->seg_buf.back()].cap >= s->seg_n.back() + kids) {
         e = hipMemcpyAsync(s->fb[s->seg_buf.back()] + s->seg_n.back(), s->fb[ob], kids * sizeof(PathItem),
                            hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return herr(e);
@@ -1303,7 +1125,7 @@ static bool chainable(const tspgpu_search *s)
 {
     // above 18 cities only with the tree bound (its frontiers are small; without
     // it a 32-city chain overflows its level buffers and reruns step by step)
-    return s->frontier && !s->noprune && s->chain && s->kernel != 3 && s->n <= (s->mst_on ? kChainMaxN : 18);
+    return s->frontier && !s->noprune && s->chain && s->n <= (s->mst_on ? kChainMaxN : 18);
 }
 
 // every `every` levels (0: never) hook(user, stream, incumbent word) enqueues
@@ -1385,12 +1207,8 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
             s->seg_n.push_back(0);
         }
     }
-    if (!fuse && tuned_or("SEARCH_CHAIN_POISON", 0) != 0) {  // tests: no slot may be read that was not written
-        for (int k = 0; k < 2 && e == hipSuccess; ++k)
-            e = hipMemsetAsync(s->fb[ob[k]], 0xFF, sizeof(PathItem) * kChainCap, st);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_tail, 0xFF, sizeof(PathItem) * s->tail_cap, st);
-        if (e != hipSuccess) return herr(e);
-    }
+    if (!fuse) e = poison_chain(s, ob, kChainCap);
+    if (e != hipSuccess) return herr(e);
     // level l reads its input count from word 4 (the seeds, l = 0) or
     // 10 + l%3, writes 10 + (l+1)%3 and zeroes 10 + (l+2)%3
     if (fuse && hooks && 1 % every == 0) {  // (level 0 ran in the seeds' launch)
@@ -1405,7 +1223,7 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
         a.fin = a.fseg[0];
         a.fin_count = l == 0 ? (uint32_t)s->local_items : (uint32_t)kChainCap;  // (the grid's bound)
         a.fin_count_dev = reinterpret_cast<const unsigned int *>(s->d_words + (l == 0 ? 4 : 10 + l % 3));
-        a.fin_cap = (uint32_t)std::min<size_t>(l == 0 ? s->fb_cap[s->seg_buf[0]] : s->fb_cap[ob[(l - 1) & 1]],
+        a.fin_cap = (uint32_t)std::min<size_t>(l == 0 ? s->fb[s->seg_buf[0]].cap : s->fb[ob[(l - 1) & 1]].cap,
                                                UINT32_MAX);
         a.out_count = reinterpret_cast<unsigned int *>(s->d_words + 10 + (l + 1) % 3);
         a.out_next = reinterpret_cast<unsigned int *>(s->d_words + 10 + (l + 2) % 3);
@@ -1466,70 +1284,8 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
     if (e == hipSuccess) e = hipMemsetAsync(s->d_words + 13, 0, 8, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(s->d_words + 1, s->d_words + 14, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && s->d_tie) {
-        constexpr size_t kTieBytes = sizeof(TieSlot) * kTieSlots;
-        e = hipMemsetAsync(s->d_tie, 0xFF, kTieBytes, st);
-        if (e == hipSuccess) e = hipMemsetAsync(tie_words(s), 0, 8 * sizeof(unsigned long long), st);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_stats, 0, kStatBytes, st);
+    if (e == hipSuccess) e = reset_tie_stats(s);
     return herr(e);
-}
-
-// The whole search in ONE persistent launch (kernel 3): seeds decoded on the
-// fly, work handed between lanes through a device ring, no rounds.
-static int run_persist(tspgpu_search *s)
-{
-    (void)hipSetDevice(s->ctx->device);
-    hipStream_t st = s->ctx->stream;
-    hipError_t e = hipSuccess;
-    if (!s->d_ps) e = hipMalloc((void **)&s->d_ps, sizeof(PersistState));
-    if (e == hipSuccess && !s->d_ring)
-        e = hipMalloc((void **)&s->d_ring, (size_t)s->ring_cap * kRingWords * sizeof(unsigned long long));
-    if (e != hipSuccess) return herr(e);
-    const bool f64 = s->dtype == TSPGPU_F64;
-    const size_t lds = search_lds_bytes(s->n, f64, 3);
-    const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / lds)));
-    const int grid = s->ctx->cu_count * per_cu;
-    PersistState h{};
-    h.work.v = s->local_items;
-    int wall_khz = 0;
-    if (hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, s->ctx->device) != hipSuccess || wall_khz <= 0)
-        wall_khz = 100000;
-    SearchArgs a = args_of(s);
-    a.kernel = 3;
-    a.ps = s->d_ps;
-    a.ring = s->d_ring;
-    a.ring_mask = s->ring_cap - 1;
-    // every resident wave may reserve up to 64 tickets between two capacity checks
-    a.ring_margin = (uint32_t)std::min<uint64_t>((uint64_t)grid * (kSearchThreads / 64) * 64, s->ring_cap / 2);
-    a.hungry = s->hungry;
-    a.min_split = s->min_split;
-    a.wall_limit = (unsigned long long)(s->wall_s * wall_khz * 1000.0);
-    // tags of a previous launch would match this launch's tickets: clear the ring
-    e = hipMemcpyAsync(s->d_ps, &h, sizeof h, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(s->d_ring, 0, (size_t)s->ring_cap * kRingWords * sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_words, 0, 8, st);
-    if (e != hipSuccess) return herr(e);
-    (void)hipEventRecord(s->e0, st);
-    e = launch_persist(a, f64, grid);
-    (void)hipEventRecord(s->e1, st);
-    if (e != hipSuccess) return herr(e);
-    e = hipMemcpyAsync(&h, s->d_ps, sizeof h, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return herr(e);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
-    s->pending = 0;
-    s->rounds = 1;
-    if (tuned("SEARCH_DEBUG", nullptr))
-        std::fprintf(stderr, "persist: grid %d seeds %llu/%llu head %llu tail %llu consumed %llu work %llu abort %llu ms %.3f\n",
-                     grid, h.seed_cursor.v, (unsigned long long)s->local_items, h.head.v, h.tail.v, h.consumed.v,
-                     h.work.v, h.abort.v, ms);
-    if (h.abort.v & 1u) return -ETIMEDOUT;
-    if (h.abort.v) return -EIO;
-    if (h.work.v != 0) return -EIO;  // every item must have finished
-    return 0;
 }
 
 // Exhaustive enumeration in ONE launch (enum.hip): a lane per depth-(N-6)
@@ -1576,7 +1332,6 @@ int tspgpu_search_run_all(tspgpu_search *s)
 {
     if (!s) return -EINVAL;
     if (s->noprune && s->enum_kernel) return run_enum(s, false);
-    if (s->kernel == 3 && !s->noprune) return run_persist(s);
     s->fresh = false;
     if (s->nshards == 1 && chainable(s)) {
         bool done = false;
@@ -1613,7 +1368,7 @@ int tspgpu_search_chain(tspgpu_search *s, int exchange_every, tspgpu_level_hook 
     }
     if (!chainable(s)) {
         // the same number of exchanges as a chained shard would enqueue
-        const int levels = s->frontier ? s->n - 1 - s->tail_len - s->depth : 0;
+        const int levels = s->frontier ? s->n - 1 - s->opt.tail_len - s->depth : 0;
         const int hooks = hook && exchange_every > 0 && levels > 1 ? (levels - 1) / exchange_every : 0;
         for (int k = 0; k < hooks; ++k) hook(user, s->ctx->stream, s->d_words + 1);
         return 0;
@@ -1707,13 +1462,7 @@ int tspgpu_search_reset_records(tspgpu_search *s, unsigned int capacity)
     (void)hipSetDevice(s->ctx->device);
     hipError_t e = hipStreamSynchronize(s->ctx->stream);
     if (e == hipSuccess && capacity > s->rec_cap) {
-        if (capacity > s->rec_alloc) {
-            (void)hipFree(s->d_rec);
-            s->d_rec = nullptr;
-            s->rec_alloc = 0;
-            e = hipMalloc((void **)&s->d_rec, sizeof(SearchRecord) * (size_t)capacity);
-            if (e == hipSuccess) s->rec_alloc = capacity;
-        }
+        if (capacity > s->d_rec.cap) e = dev_alloc(s->d_rec, capacity);
         if (e == hipSuccess) s->rec_cap = capacity;
     }
     if (e == hipSuccess) e = hipMemset(s->d_words + 3, 0, 8);

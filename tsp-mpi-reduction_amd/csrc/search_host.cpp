@@ -610,6 +610,171 @@ int tie_tour(const void *dist, int dtype, int n, uint64_t w0, uint64_t w1, uint6
     return rc;
 }
 
+bool is_symmetric(const void *dist, int dtype, int n)
+{
+    const bool f64 = dtype == TSPGPU_F64;
+    bool sym = true;
+    for (int i = 0; i < n && sym; ++i)
+        for (int j = 0; j < i && sym; ++j)
+            sym = f64 ? static_cast<const double *>(dist)[i * n + j] == static_cast<const double *>(dist)[j * n + i]
+                      : static_cast<const int32_t *>(dist)[i * n + j] == static_cast<const int32_t *>(dist)[j * n + i];
+    return sym;
+}
+
+uint64_t falling(int N, int D)
+{
+    uint64_t p = 1;
+    for (int l = 0; l < D; ++l) p *= (uint64_t)(N - l);
+    return p;
+}
+
+uint64_t shard_items(uint64_t items, uint32_t shard, uint32_t nshards)
+{
+    return items / nshards + (items % nshards > (uint64_t)shard ? 1 : 0);
+}
+
+SeedPlan plan_seeds(int n, int shard, int nshards, int depth, uint64_t grid_lanes, int cu_count,
+                    const PlanOptions &o, bool symmetric, bool enum_shard)
+{
+    const int N = n - 1;
+    // seed depth: the smallest D with at least one prefix per lane of the
+    // whole grid (the rounds split whatever is still too coarse), at most
+    // N-1, at least 1, and < 2^31 prefixes
+    const uint64_t lanes = grid_lanes * (uint64_t)nshards;
+    const bool auto_depth = depth <= 0;
+    if (depth <= 0) {
+        depth = 1;
+        while (depth < N - 1 && falling(N, depth + 1) < (1ull << 31) && falling(N, depth) < lanes) ++depth;
+    }
+    if (depth > N - 1) depth = N - 1;
+    while (depth > 1 && falling(N, depth) >= (1ull << 31)) --depth;
+    SeedPlan p{};
+    p.frontier = o.tail_len && o.kernel == 2 && N - o.tail_len > depth && !enum_shard;
+    // the frontier search expands level by level with its own bounds: a
+    // smaller seed set (~64 prefixes per CU) costs less than the round
+    // kernels' one-per-lane (measured at n = 16: depth 4 vs 5, 0.14 vs 0.16 ms)
+    if (p.frontier && auto_depth) {
+        const uint64_t want = (uint64_t)cu_count * 64 * nshards;
+        int d = 1;
+        while (d < depth && falling(N, d) < want) ++d;
+        // several shards: one level deeper, so that the heavy subtrees near
+        // the optimum spread over the shards (n = 30 random, 8 shards: node
+        // imbalance max/mean 1.91 at depth 4, 1.20 at depth 5;
+        // profiles/r02/k2_shard_balance_depth.log)
+        // Not with the tree bound (symmetric matrices): it leaves no heavy
+        // subtree to spread, and the deeper seed level, bounded only by B0/B1,
+        // costs more than it balances (n = 32 seed 35, 2 shards: 5.0e7 nodes
+        // per shard vs 7.1e5 for one GPU; profiles/r02/k2_shard_depth_tree.log)
+        const bool tree = o.use_mst && o.use_two_edge && symmetric;
+        if (nshards > 1 && !tree && d + 1 < N - o.tail_len && falling(N, d + 1) < (1ull << 31)) ++d;
+        depth = d;
+    }
+    p.depth = depth;
+    p.items = falling(N, depth);
+    p.local_items = shard_items(p.items, (uint32_t)shard, (uint32_t)nshards);
+    return p;
+}
+
+void build_bound_tables(const void *dist, int dtype, int n, bool symmetric, const SeedPlan &plan,
+                        const PlanOptions &o, BoundTables &t)
+{
+    const bool f64 = dtype == TSPGPU_F64;
+    // cheapest incoming edge per city; f64 rounded DOWN to a 2^-20 grid
+    if (f64) {
+        const double *d = static_cast<const double *>(dist);
+        t.amin_d.resize(n);
+        for (int x = 0; x < n; ++x) {
+            double m = INFINITY;
+            for (int i = 0; i < n; ++i)
+                if (i != x) m = std::min(m, d[i * n + x]);
+            t.amin_d[x] = std::ldexp(std::floor(std::ldexp(m, 20)), -20);
+        }
+    } else {
+        const int32_t *d = static_cast<const int32_t *>(dist);
+        t.amin_i.resize(n);
+        for (int x = 0; x < n; ++x) {
+            int32_t m = INT32_MAX;
+            for (int i = 0; i < n; ++i)
+                if (i != x) m = std::min(m, d[i * n + x]);
+            t.amin_i[x] = m;
+        }
+    }
+    t.sym = o.use_two_edge && symmetric ? 1 : 0;
+    t.mst_on = false;
+    if (!t.sym) return;
+    // two-edge bound (symmetric matrices): per city x, b[x] = half the sum of
+    // its two cheapest incident edges, e[x] = half its cheapest, rounded down
+    // to the bound's grid (f64: 2^-20, exact sums; i32: integers)
+    if (f64)
+        t.bnd2_d.assign(2 * n, 0.0);
+    else
+        t.bnd2_i.assign(2 * n, 0);
+    std::vector<double> D((size_t)n * n);
+    for (int i = 0; i < n * n; ++i)
+        D[i] = f64 ? static_cast<const double *>(dist)[i] : (double)static_cast<const int32_t *>(dist)[i];
+    std::vector<double> pi(n, 0.0);
+    std::vector<double> hk_pi;  // Held-Karp weights of the tree bound
+    // the tree bound's weights on a second thread meanwhile (host time
+    // at n = 32: 1.3 ms beside lagrange_pi's 0.45 ms)
+    // (only if some path can reach it: the expand kernel applies the
+    // tree bound to paths with >= mst_min_rem cities left, and the
+    // frontier starts at the seed depth — at n = 16 none does, and
+    // the weights cost 0.22 ms of host time, profiles/r03/k2_variants.log)
+    const bool want_tree = o.use_mst && n >= 4 && plan.frontier && n - 1 - plan.depth >= o.mst_min_rem;
+    std::thread ht;
+    bool threaded = false;
+    if (want_tree && n >= 20) {  // (smaller: a thread costs more than it saves)
+        try {
+            ht = std::thread([&] { held_karp_pi(D, n, hk_pi); });
+            threaded = true;
+        } catch (...) {
+        }
+    }
+    if (o.use_lagrange) lagrange_pi(D, n, pi);
+    if (threaded)
+        ht.join();
+    else if (want_tree)
+        held_karp_pi(D, n, hk_pi);
+    for (int x = 0; x < n; ++x) {
+        double m1 = INFINITY, m2 = INFINITY;  // the two cheapest d'[x][y] = d + pi_x + pi_y
+        for (int y = 0; y < n; ++y) {
+            if (y == x) continue;
+            const double v = D[(size_t)x * n + y] + pi[x] + pi[y];
+            if (v < m1) {
+                m2 = m1;
+                m1 = v;
+            } else if (v < m2) {
+                m2 = v;
+            }
+        }
+        // b = (m1 + m2)/2 - 2 pi_x, e = m1/2 - pi_x: lower bounds, so
+        // a margin for the double rounding of d + pi + pi, then DOWN
+        // to the grid
+        const double bx = (m1 + m2) * 0.5 - 2.0 * pi[x], ex = m1 * 0.5 - pi[x];
+        const double mg = 1e-9 * (std::fabs(m1) + std::fabs(m2) + 4.0 * std::fabs(pi[x]) + 1.0);
+        if (f64) {
+            t.bnd2_d[2 * x] = std::ldexp(std::floor(std::ldexp(bx - mg, 20)), -20);
+            t.bnd2_d[2 * x + 1] = std::ldexp(std::floor(std::ldexp(ex - mg, 20)), -20);
+        } else {
+            t.bnd2_i[2 * x] = (int32_t)std::floor(bx - mg);
+            t.bnd2_i[2 * x + 1] = (int32_t)std::floor(ex - mg);
+        }
+    }
+    // tree bound: d' and pi as doubles, and a margin far above the rounding of
+    // the device's sums of <= 2n + 2 such terms
+    t.mst_on = o.use_mst && n >= 4 && (int)hk_pi.size() == n;
+    if (!t.mst_on) return;
+    t.mt.assign((size_t)n * n + n + 1, 0.0);
+    double mx = 0.0, ps = 0.0;
+    for (int x = 0; x < n; ++x)
+        for (int y = 0; y < n; ++y) {
+            t.mt[(size_t)x * n + y] = D[(size_t)x * n + y] + hk_pi[x] + hk_pi[y];
+            mx = std::max(mx, std::fabs(t.mt[(size_t)x * n + y]));
+        }
+    for (int x = 0; x < n; ++x) t.mt[(size_t)n * n + x] = hk_pi[x], ps += std::fabs(hk_pi[x]);
+    t.mt[(size_t)n * n + n] = 1e-9 * ((n + 2) * mx + 2.0 * ps + 1.0);
+}
+
 }  // namespace host
 }  // namespace tspgpu
 

@@ -45,5 +45,48 @@ struct RecordsPrefix {
     void *next_user;
 };
 int records_prefix(void *user, const double *d, int n, const int32_t *t, int j, double *g);
+
+// ---------------------------------------------------------------------------
+// The plan of a search (search_abi.cpp search_create): the seed depth and the
+// host tables of its bounds, from the instance and the knobs alone.
+struct PlanOptions {           // the knobs the plan reads; the defaults are the product
+    int kernel = 2;            // SEARCH_KERNEL: 2 lock-step DFS, 1 branching DFS
+    int tail_len = 6;          // SEARCH_TAIL: 5/6 frontier search, 0 DFS rounds
+    bool use_two_edge = true;  // SEARCH_TWO_EDGE
+    bool use_lagrange = true;  // SEARCH_LAGRANGE
+    bool use_mst = true;       // SEARCH_MST
+    int mst_min_rem = 12;      // SEARCH_MST_MINREM
+};
+// dist[i][j] == dist[j][i] for all i, j
+bool is_symmetric(const void *dist, int dtype, int n);
+// N (N-1) ... (N-D+1): the depth-D prefixes of N inner cities
+uint64_t falling(int N, int D);
+// the prefixes p = i * nshards + shard below `items`
+uint64_t shard_items(uint64_t items, uint32_t shard, uint32_t nshards);
+struct SeedPlan {
+    int depth;             // seed prefix depth
+    uint64_t items;        // falling(n - 1, depth), < 2^31
+    uint64_t local_items;  // this shard's share
+    bool frontier;         // frontier search (else the DFS rounds)
+};
+// depth <= 0: automatic.  grid_lanes: lanes of one shard's round grid;
+// symmetric: is_symmetric(dist); enum_shard: the enumeration kernel will run
+// this shard (no frontier).
+SeedPlan plan_seeds(int n, int shard, int nshards, int depth, uint64_t grid_lanes, int cu_count,
+                    const PlanOptions &o, bool symmetric, bool enum_shard);
+// The bound tables, as uploaded: amin (cheapest incoming edge per city), and
+// for symmetric matrices bnd2 (the two-edge pairs {b[x], e[x]}) and mt (the
+// tree bound: d', pi and the margin, SearchArgs::mst) — all lower bounds, the
+// f64 ones rounded DOWN to a 2^-20 grid.  The f64 or the i32 vectors are
+// filled, by dtype.
+struct BoundTables {
+    std::vector<double> amin_d, bnd2_d;
+    std::vector<int32_t> amin_i, bnd2_i;
+    int sym = 0;             // use_two_edge && symmetric: bnd2 is built
+    std::vector<double> mt;  // n*n + n + 1 doubles when mst_on
+    bool mst_on = false;
+};
+void build_bound_tables(const void *dist, int dtype, int n, bool symmetric, const SeedPlan &plan,
+                        const PlanOptions &o, BoundTables &t);
 }  // namespace host
 }  // namespace tspgpu

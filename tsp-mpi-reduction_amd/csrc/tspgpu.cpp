@@ -451,7 +451,6 @@ const char *tspgpu_strerror(int code)
     case -EDEADLK: return "the reference's mergeBlocks would never terminate for these paths";
     case -EOVERFLOW: return "too many tied optimal tours to enumerate above K1-wide's 31 cities";
     case -ENOSPC: return "output buffer too small";
-    case -ETIMEDOUT: return "search watchdog expired (TSPGPU_SEARCH_WALL_S)";
     default: return "unknown error";
     }
 }

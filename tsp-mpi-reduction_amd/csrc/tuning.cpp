@@ -28,11 +28,7 @@ Knob g_knobs[] = {
     // K1-wide (hkwide.hip)
     {"WIDE_PULL", false, 0},       // 1: per-destination layer form everywhere, 0: row-owner form
     // K2 (search_abi.cpp, read at search creation / run)
-    {"SEARCH_KERNEL", false, 0},   // round kernel: 1 branching DFS, 2 lock-step DFS, 3 persistent
-    {"SEARCH_HUNGRY", false, 0},
-    {"SEARCH_MIN_SPLIT", false, 0},
-    {"SEARCH_WALL_S", false, 0},
-    {"SEARCH_RING_LOG2", false, 0},
+    {"SEARCH_KERNEL", false, 0},   // round kernel: 1 branching DFS, else 2 lock-step DFS
     {"SEARCH_REFILL", false, 0},
     {"SEARCH_TAIL", false, 0},     // frontier tail length 5/6, 0: DFS rounds
     {"SEARCH_SUFFIX", false, 0},

@@ -2,7 +2,8 @@
 // CPU halves of the product — the host parity layer (host/tsp_host.cpp:
 // generator, distribution, mergeBlocks, reduction-tree replay) and K2's host
 // algorithms (csrc/search_host.cpp: input check, multi-start tour, Lagrangian
-// and 1-tree weights, the tie rule over the optimal set) — driven over a grid
+// and 1-tree weights, the tie rule over the optimal set, the search's plan:
+// seed depth and bound tables) — driven over a grid
 // of sizes and edge cases, with the results compared against the CPU oracle
 // (oracle/oracle.c, the checker, compiled into this test binary only).  Any
 // sanitizer report aborts (-fno-sanitize-recover=all); a mismatch exits 1.
@@ -97,6 +98,83 @@ void check_merge(int L1, int L2)
     }
 }
 
+int tree_tables = 0;  // tree tables check_bound_tables saw (main: some must have been built)
+
+// build_bound_tables (csrc/search_host.cpp) against the tables' definitions;
+// d = the f64 view of dist.  A bound that is not a lower bound prunes the
+// optimum, so for n <= 12 the sums are compared with the oracle's optimum —
+// exactly: each entry is rounded DOWN by a margin far above the sums' rounding.
+void check_bound_tables(const void *dist, int dtype, int n, const std::vector<double> &d)
+{
+    using namespace tspgpu::host;
+    const bool integer = dtype == TSPGPU_I32;
+    bool sym = true;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) sym = sym && d[(size_t)i * n + j] == d[(size_t)j * n + i];
+    expect(is_symmetric(dist, dtype, n) == sym, "is_symmetric", n, integer);
+    double opt = 0.0;
+    if (n <= 12) {
+        std::vector<int32_t> ot(n + 1);
+        oracle_solve_block(d.data(), n, &opt, ot.data());
+    }
+    // the default knobs, no Lagrangian weights, and the tree bound from 2 cities left
+    for (int cfg = 0; cfg < 3; ++cfg) {
+        PlanOptions o;
+        if (cfg == 1) o.use_lagrange = false;
+        if (cfg == 2) o.mst_min_rem = 2;
+        const SeedPlan plan = plan_seeds(n, 0, 1, 0, (uint64_t)256 * 8 * 256, 256, o, sym, false);
+        BoundTables t;
+        build_bound_tables(dist, dtype, n, sym, plan, o, t);
+        expect(t.sym == (sym ? 1 : 0), "tables sym", n, integer, cfg);
+        double asum = 0.0;
+        for (int x = 0; x < n; ++x) {
+            double m = INFINITY;
+            for (int i = 0; i < n; ++i)
+                if (i != x) m = std::fmin(m, d[(size_t)i * n + x]);
+            if (integer) {
+                expect((int)t.amin_i.size() == n && (double)t.amin_i[x] == m, "amin i32", n, x, cfg);
+                asum += t.amin_i[x];
+            } else {
+                const double a = (int)t.amin_d.size() == n ? t.amin_d[x] : -1.0, g = std::ldexp(a, 20);
+                expect(g == std::floor(g) && m - a >= 0.0 && m - a < 0x1p-20, "amin f64 grid", n, x, cfg);
+                asum += a;
+            }
+        }
+        if (n <= 12) expect(asum <= opt, "sum of amin <= optimum", n, integer, cfg);
+        if (!sym) {
+            expect(t.bnd2_d.empty() && t.bnd2_i.empty() && t.mt.empty() && !t.mst_on, "asymmetric: no bnd2, no tree", n,
+                   integer, cfg);
+            continue;
+        }
+        expect((integer ? t.bnd2_i.size() : t.bnd2_d.size()) == (size_t)2 * n, "bnd2 size", n, integer, cfg);
+        if (n <= 12) {
+            double bsum = 0.0;
+            for (int x = 0; x < n; ++x) bsum += integer ? (double)t.bnd2_i[2 * x] : t.bnd2_d[2 * x];
+            expect(bsum <= opt, "sum of b <= optimum", n, integer, cfg);
+        }
+        expect(t.mst_on == !t.mt.empty(), "tree flag", n, integer, cfg);
+        if (!t.mst_on) continue;
+        ++tree_tables;
+        expect(t.mt.size() == (size_t)n * n + n + 1, "tree size", n, integer, cfg);
+        const double *pi = t.mt.data() + (size_t)n * n;
+        const double mg = t.mt[(size_t)n * n + n];
+        for (int x = 0; x < n; ++x)
+            for (int y = 0; y < n; ++y) {
+                const double v = d[(size_t)x * n + y] + pi[x] + pi[y], w = t.mt[(size_t)x * n + y];
+                expect(std::memcmp(&v, &w, 8) == 0, "tree d'", n, x, y);
+                // symmetric up to the two summation orders: fl(fl(d + pi_x) + pi_y)
+                // and fl(fl(d + pi_y) + pi_x) each lie within (2u + u^2) S of the real
+                // sum, S = |d| + |pi_x| + |pi_y|, u = 2^-53, so they differ by less
+                // than 8u S (measured: up to 2.1u S, on one pair in five) — and by
+                // less than the table's margin, which is what covers it on the device
+                const double S = std::fabs(d[(size_t)x * n + y]) + std::fabs(pi[x]) + std::fabs(pi[y]);
+                const double asym = std::fabs(w - t.mt[(size_t)y * n + x]);
+                expect(asym <= 0x1p-50 * S && asym < mg, "tree symmetric", n, x, y);
+            }
+        expect(std::isfinite(mg) && mg > 0.0, "tree margin", n, integer, cfg);
+    }
+}
+
 // K2 host algorithms on random instances: the multi-start tour is a
 // permutation whose cost is its left fold, >= the optimum; the tie rule on the
 // optimal tour alone returns that tour; the weights are finite
@@ -154,6 +232,43 @@ void check_search_host(int n, bool integer)
     // invalid inputs are refused, not read out of bounds
     expect(tspgpu::host::validate_search(dist, dtype, 2) != 0, "validate n=2", n);
     expect(tspgpu_select_tour(dist, dtype, n, nullptr, 0, 0, t.data()) != 0, "select empty", n);
+    // the bound tables of the search's plan: as generated (symmetric), then
+    // with one entry raised (asymmetric)
+    check_bound_tables(dist, dtype, n, d);
+    d[1 * n + 2] += 3.0;
+    di[1 * n + 2] += 3;
+    check_bound_tables(dist, dtype, n, d);
+}
+
+// plan_seeds over sizes, shard counts and requested depths (256 CUs, 8 blocks
+// of 256 lanes per CU): depth within 1..N-1, items = N(N-1)..(N-depth+1) below
+// 2^31 and split over the shards without loss, a frontier only with levels to
+// expand, a requested depth honoured up to the clamps
+void check_plan_seeds(int n)
+{
+    using namespace tspgpu::host;
+    const int N = n - 1, cus = 256;
+    const uint64_t lanes = (uint64_t)cus * 8 * 256;
+    const PlanOptions o;
+    for (int nshards : {1, 2, 3, 8})
+        for (int req : {0, 1, 3})
+            for (int variant = 0; variant < 4; ++variant) {
+                const bool symmetric = variant & 1, enum_shard = variant & 2;
+                uint64_t sum = 0, items = 0;
+                for (int shard = 0; shard < nshards; ++shard) {
+                    const SeedPlan p = plan_seeds(n, shard, nshards, req, lanes, cus, o, symmetric, enum_shard);
+                    expect(p.depth >= 1 && p.depth <= N - 1, "plan depth range", n, nshards, req);
+                    uint64_t f = 1;
+                    for (int l = 0; l < p.depth; ++l) f *= (uint64_t)(N - l);
+                    expect(p.items == f && f < (1ull << 31), "plan items", n, nshards, req);
+                    expect(!p.frontier || (N - o.tail_len > p.depth && !enum_shard), "plan frontier", n, nshards, req);
+                    // (N <= 31: a depth of 3 is below 2^31 prefixes, so only N - 1 clamps it)
+                    if (req > 0) expect(p.depth == (req < N - 1 ? req : N - 1), "plan requested depth", n, nshards, req);
+                    sum += p.local_items;
+                    items = p.items;
+                }
+                expect(sum == items, "plan shard split", n, nshards, req);
+            }
 }
 
 }  // namespace
@@ -168,6 +283,8 @@ int main()
         for (int L2 : {3, 6, 13}) check_merge(L1, L2);
     for (int n = 3; n <= 32; n += (n < 12 ? 1 : 5))
         for (bool integer : {false, true}) check_search_host(n, integer);
+    expect(tree_tables > 0, "no tree table was built");
+    for (int n = 4; n <= 32; ++n) check_plan_seeds(n);
     std::printf("check_host: %s (%d mismatches)\n", failures ? "FAILED" : "ok", failures);
     return failures ? 1 : 0;
 }
