@@ -115,6 +115,64 @@ int tspgpu_solve_blocks_i32(tspgpu_ctx *ctx, const int32_t *dist, int n, int nbl
 int tspgpu_solve_blocks_i32_device(tspgpu_ctx *ctx, const int32_t *d_dist, int n, int nblocks, int32_t *d_cost,
                                    int32_t *d_tour, void *hip_stream);
 
+/* ---------------------------------------------------------------------------
+ * Ragged batches: blocks of DIFFERENT city counts in one call, every block
+ * validated on the device, one status per block.  block b is the n[b] x n[b]
+ * row-major matrix at element offset[b] of the distance array (elements of
+ * dtype: TSPGPU_F64 doubles or TSPGPU_I32 int32).  Offsets need no alignment
+ * beyond the element's, and may overlap, repeat and come in any order.
+ *
+ * One device pass validates every block while it gathers it into a
+ * contiguous bucket per size; every non-empty bucket is then one ordinary K1
+ * launch, in ascending n (the kernels and dispatch of tspgpu_solve_blocks,
+ * unchanged); a second pass writes the answers back in caller order.
+ *
+ * The contract.  The call returns 0 however many blocks are bad; status[b]
+ * says which.
+ *   status[b] == 0: cost[b] (dtype's type) and tour row b equal, bit for bit,
+ *     what tspgpu_solve_blocks / tspgpu_solve_blocks_i32 returns for that
+ *     matrix alone — hence tsp()'s.  Row b of the tour array starts at
+ *     b * tour_stride: tspgpu_tour_length(n[b]) entries, then -1 up to
+ *     tour_stride.
+ *   otherwise status[b] equals tspgpu_validate(matrix, n[b], 1, strict) /
+ *     tspgpu_validate_i32(...): -EINVAL (n[b] outside [2, 20] (strict: 16),
+ *     offset[b] < 0 — such a block's matrix is never read — or a negative,
+ *     non-finite or -0.0 element), -ERANGE (n * max(d) >= INT_MAX); or it is
+ *     -EIO (the kernel found no tour; never seen on validated data).  Its
+ *     cost is NaN (f64) or -1 (int32) and its whole tour row is -1.  A bad
+ *     block costs only itself: its neighbours are solved.
+ * Called with one n for every block this is the validated form of
+ * tspgpu_solve_blocks_device.
+ *
+ * Call-level errors (nothing is launched, no output is written): -EINVAL for
+ * a NULL context, a NULL pointer with nblocks > 0, nblocks < 0, an unknown
+ * dtype, or tour_stride < (largest in-range n[b]) + 1; -ENOMEM, -ENODEV, -EIO
+ * as elsewhere.  nblocks == 0 returns 0.
+ *
+ * After a ragged call tspgpu_last_variant / tspgpu_last_grid report the LAST
+ * bucket launched, i.e. the one of the largest in-range n (unchanged when no
+ * block was in range).
+ * ------------------------------------------------------------------------- */
+#define TSPGPU_F64 0
+#define TSPGPU_I32 1
+/* Device-pointer form, asynchronous on `hip_stream`.  d_dist, d_cost, d_tour
+ * (nblocks * tour_stride int32) and d_status (nblocks int32) are device
+ * pointers on the context's device; offset[] and n[] are HOST arrays, read
+ * before the call returns.  Every in-range block's n*n elements at
+ * d_dist + offset[b] must be readable device memory.  The staging buckets
+ * are the context's, like the K1 workspace: a later ragged or K1 call on
+ * another stream waits (hipStreamWaitEvent) for this call's last kernel. */
+int tspgpu_solve_ragged_device(tspgpu_ctx *ctx, const void *d_dist, int dtype, const int64_t *offset,
+                               const int32_t *n, int nblocks, void *d_cost, int32_t *d_tour, int tour_stride,
+                               int32_t *d_status, void *hip_stream);
+/* Host-pointer form, synchronous.  Uploads the covering extent
+ * [min offset, max(offset + n*n)) of the in-range blocks in one copy — gaps
+ * between blocks travel too, so this form is meant for packed (or nearly
+ * packed) arrays — runs the device form on the context's stream and copies
+ * cost, tour and status back. */
+int tspgpu_solve_ragged(tspgpu_ctx *ctx, const void *dist, int dtype, const int64_t *offset, const int32_t *n,
+                        int nblocks, void *cost_out, int32_t *tour_out, int tour_stride, int32_t *status_out);
+
 /* Context-free convenience form (uses a per-thread default context on the
  * current device, created on first use). */
 int tspgpu_solve(const double *dist, int n, int nblocks, double *cost_out, int32_t *tour_out,
@@ -199,8 +257,7 @@ int tspgpu_wide_last_dtype(const tspgpu_ctx *ctx);
  * integer-matrix extension: d >= 0, n * max(d) < 2^30).
  * ------------------------------------------------------------------------- */
 #define TSPGPU_SEARCH_MAX_CITIES 32
-#define TSPGPU_F64 0
-#define TSPGPU_I32 1
+/* (value types TSPGPU_F64 / TSPGPU_I32: defined above, with the ragged batches) */
 
 /* One recorded complete tour: cost (IEEE bits of the f64 cost, or the
  * integer cost) and the inner cities t1..tN (N = n-1) in visiting order. */

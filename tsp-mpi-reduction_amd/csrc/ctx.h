@@ -56,6 +56,28 @@ struct tspgpu_ctx {
     bool split_overflow = false;
     hipStream_t k1_last_stream = nullptr;
     bool k1_launched = false;
+    // Ragged batches (tspgpu_solve_ragged*, ragged_plan.h): the staging
+    // buckets K1 solves from and into, the per-block descriptors and statuses.
+    // Per context like the K1 workspace and under the same ordering rule
+    // (ev_k1_done is recorded behind the scatter kernel too).  The descriptors
+    // are uploaded from a pinned buffer; ev_rg_desc fires when that copy has
+    // read it, and the next ragged call waits for it before it writes there.
+    void *d_rg_desc = nullptr;
+    size_t rg_desc_bytes = 0;
+    void *d_rg_dist = nullptr;
+    size_t rg_dist_bytes = 0;
+    void *d_rg_cost = nullptr;
+    size_t rg_cost_bytes = 0;
+    int32_t *d_rg_tour = nullptr;
+    size_t rg_tour_bytes = 0;
+    int32_t *d_rg_status = nullptr;
+    size_t rg_status_bytes = 0;
+    int32_t *d_rg_ostatus = nullptr;  // the host form's status output (its cost / tour use d_cost / d_tour)
+    size_t rg_ostatus_bytes = 0;
+    void *h_rg_desc = nullptr;        // pinned
+    size_t h_rg_desc_bytes = 0;
+    hipEvent_t ev_rg_desc = nullptr;
+    bool rg_desc_pending = false;
     char name[256] = {0};
     std::mutex mu;
     // K1-wide per-context cache (buffers of the last (n, value type)), hkwide_impl.h

@@ -25,6 +25,7 @@
 #include "ctx.h"
 #include "heldkarp.h"
 #include "k1_cfg.h"
+#include "ragged.h"
 #include "xfer.h"
 
 namespace tspgpu {
@@ -615,6 +616,11 @@ void tspgpu_ctx_release(tspgpu_ctx *c)
     if (c->d_dist) (void)hipFree(c->d_dist);
     if (c->d_cost) (void)hipFree(c->d_cost);
     if (c->d_tour) (void)hipFree(c->d_tour);
+    for (void *p : {c->d_rg_desc, c->d_rg_dist, c->d_rg_cost, (void *)c->d_rg_tour, (void *)c->d_rg_status,
+                    (void *)c->d_rg_ostatus})
+        if (p) (void)hipFree(p);
+    if (c->h_rg_desc) (void)hipHostFree(c->h_rg_desc);
+    if (c->ev_rg_desc) (void)hipEventDestroy(c->ev_rg_desc);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     if (c->ev_k1_done) (void)hipEventDestroy(c->ev_k1_done);
@@ -834,6 +840,11 @@ int tspgpu_stream_destroy(tspgpu_ctx *c, void *stream)
     if (!stream) return 0;
     if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
     std::lock_guard<std::mutex> g(c->mu);
+    if (c->rg_desc_pending) {
+        // (a ragged call's descriptor upload may sit on this stream: let it finish first)
+        (void)hipEventSynchronize(c->ev_rg_desc);
+        c->rg_desc_pending = false;
+    }
     if (c->k1_last_stream == (hipStream_t)stream) {
         // the next launch must not wait on an event of a destroyed stream's queue:
         // drain it and forget it
@@ -885,6 +896,149 @@ int tspgpu_device_info(const tspgpu_ctx *c, int *cu_count, char *name, int namec
     if (cu_count) *cu_count = c->cu_count;
     if (name && namecap > 0) std::snprintf(name, (size_t)namecap, "%s", c->name);
     return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Ragged batches: blocks of different sizes in one call, each
+// validated on the device.  Host plan (ragged_plan.h) -> gather + validate
+// (ragged.hip) -> one unchanged K1 launch per size bucket -> scatter.
+// ---------------------------------------------------------------------------
+namespace {
+
+int ragged_vbytes(int dtype) { return dtype == TSPGPU_F64 ? 8 : (dtype == TSPGPU_I32 ? 4 : 0); }
+
+// the call-level checks and the plan; 1: nothing to do (nblocks == 0)
+int ragged_prepare(const tspgpu_ctx *c, const void *dist, int dtype, const int64_t *offset, const int32_t *n,
+                   int nblocks, const void *cost, const void *tour, int tour_stride, const void *status,
+                   RaggedPlan *plan)
+{
+    if (!c || nblocks < 0 || !ragged_vbytes(dtype)) return -EINVAL;
+    if (nblocks == 0) return 1;
+    if (!dist || !offset || !n || !cost || !tour || !status) return -EINVAL;
+    const int rc = ragged_plan(n, offset, nblocks, c->strict, ragged_vbytes(dtype), plan);
+    if (rc) return rc;
+    if (tour_stride < plan->max_n + 1) return -EINVAL;
+    return 0;
+}
+
+// The device work of one ragged call on `stream` (c->mu held).  The plan's
+// source offsets are relative to d_dist + rebase elements (the host form
+// uploads the covering extent only).  Nothing is waited for.
+int ragged_locked(tspgpu_ctx *c, const void *d_dist, int vbytes, RaggedPlan &plan, int64_t rebase, void *d_cost,
+                  int32_t *d_tour, int tour_stride, int32_t *d_status, hipStream_t stream)
+{
+    const int nblocks = plan.nblocks;
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    int rc = 0;
+    const size_t desc_bytes = (size_t)nblocks * sizeof(RaggedDesc);
+    if ((rc = ensure(&c->d_rg_desc, &c->rg_desc_bytes, desc_bytes))) return rc;
+    if ((rc = ensure(&c->d_rg_dist, &c->rg_dist_bytes, (size_t)plan.dist_elems * vbytes))) return rc;
+    if ((rc = ensure(&c->d_rg_cost, &c->rg_cost_bytes, (size_t)plan.cost_elems * vbytes))) return rc;
+    if ((rc = ensure(&c->d_rg_tour, &c->rg_tour_bytes, (size_t)plan.tour_elems * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(&c->d_rg_status, &c->rg_status_bytes, (size_t)nblocks * sizeof(int32_t)))) return rc;
+    hipError_t e = hipSuccess;
+    // the pinned descriptor buffer: the previous call's upload must have read it
+    if (c->rg_desc_pending) {
+        if ((e = hipEventSynchronize(c->ev_rg_desc)) != hipSuccess) return hip_err(e);
+        c->rg_desc_pending = false;
+    }
+    if (c->h_rg_desc_bytes < desc_bytes) {
+        if (c->h_rg_desc) (void)hipHostFree(c->h_rg_desc);
+        c->h_rg_desc = nullptr;
+        c->h_rg_desc_bytes = 0;
+        if ((e = hipHostMalloc(&c->h_rg_desc, desc_bytes, hipHostMallocDefault)) != hipSuccess) {
+            c->h_rg_desc = nullptr;
+            return hip_err(e);
+        }
+        c->h_rg_desc_bytes = desc_bytes;
+    }
+    if (!c->ev_rg_desc && (e = hipEventCreateWithFlags(&c->ev_rg_desc, hipEventDisableTiming)) != hipSuccess)
+        return hip_err(e);
+    if (!c->ev_k1_done && (e = hipEventCreateWithFlags(&c->ev_k1_done, hipEventDisableTiming)) != hipSuccess)
+        return hip_err(e);
+    RaggedDesc *hd = static_cast<RaggedDesc *>(c->h_rg_desc);
+    for (int b = 0; b < nblocks; ++b) {
+        hd[b] = plan.desc[b];
+        if (!hd[b].pre) hd[b].src -= rebase;
+    }
+    // the staging buffers are the context's: behind the previous K1 or ragged
+    // launch when that ran on another stream (solve_device_locked's rule)
+    if (c->k1_launched && stream != c->k1_last_stream) {
+        if ((e = hipStreamWaitEvent(stream, c->ev_k1_done, 0)) != hipSuccess) return hip_err(e);
+    }
+    if ((e = hipMemcpyAsync(c->d_rg_desc, hd, desc_bytes, hipMemcpyHostToDevice, stream)) != hipSuccess)
+        return hip_err(e);
+    if ((e = hipEventRecord(c->ev_rg_desc, stream)) != hipSuccess) return hip_err(e);
+    c->rg_desc_pending = true;
+    const RaggedDesc *dd = static_cast<const RaggedDesc *>(c->d_rg_desc);
+    if ((e = launch_ragged_gather(vbytes, d_dist, dd, nblocks, c->d_rg_dist, c->d_rg_status, stream)) != hipSuccess)
+        return hip_err(e);
+    for (int k = kRaggedMinN; k <= kRaggedMaxN; ++k) {
+        if (!plan.count[k]) continue;
+        rc = solve_device_locked(c, static_cast<char *>(c->d_rg_dist) + (size_t)plan.dist_base[k] * vbytes, k,
+                                 plan.count[k], static_cast<char *>(c->d_rg_cost) + (size_t)plan.cost_base[k] * vbytes,
+                                 c->d_rg_tour + plan.tour_base[k], stream, vbytes);
+        if (rc) return rc;
+    }
+    e = launch_ragged_scatter(vbytes, dd, c->d_rg_status, nblocks, c->d_rg_cost, c->d_rg_tour, d_cost, d_tour,
+                              tour_stride, d_status, stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev_k1_done, stream);
+    if (e != hipSuccess) return hip_err(e);
+    c->k1_last_stream = stream;
+    c->k1_launched = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tspgpu_solve_ragged_device(tspgpu_ctx *c, const void *d_dist, int dtype, const int64_t *offset, const int32_t *n,
+                               int nblocks, void *d_cost, int32_t *d_tour, int tour_stride, int32_t *d_status,
+                               void *hip_stream)
+{
+    RaggedPlan plan;
+    const int rc = ragged_prepare(c, d_dist, dtype, offset, n, nblocks, d_cost, d_tour, tour_stride, d_status, &plan);
+    if (rc) return rc < 0 ? rc : 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    return ragged_locked(c, d_dist, ragged_vbytes(dtype), plan, 0, d_cost, d_tour, tour_stride, d_status,
+                         (hipStream_t)hip_stream);
+}
+
+int tspgpu_solve_ragged(tspgpu_ctx *c, const void *dist, int dtype, const int64_t *offset, const int32_t *n,
+                        int nblocks, void *cost_out, int32_t *tour_out, int tour_stride, int32_t *status_out)
+{
+    RaggedPlan plan;
+    int rc = ragged_prepare(c, dist, dtype, offset, n, nblocks, cost_out, tour_out, tour_stride, status_out, &plan);
+    if (rc) return rc < 0 ? rc : 0;
+    const int vbytes = ragged_vbytes(dtype);
+    std::lock_guard<std::mutex> g(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    // the covering extent of the in-range blocks in one copy (gaps travel too)
+    const size_t db = (size_t)(plan.ext_hi - plan.ext_lo) * vbytes;
+    const size_t cb = (size_t)nblocks * vbytes;
+    const size_t tb = (size_t)nblocks * tour_stride * sizeof(int32_t);
+    const size_t sb = (size_t)nblocks * sizeof(int32_t);
+    if ((rc = ensure(&c->d_dist, &c->dist_bytes, db))) return rc;
+    if ((rc = ensure(&c->d_cost, &c->cost_bytes, cb))) return rc;
+    if ((rc = ensure(&c->d_tour, &c->tour_bytes, tb))) return rc;
+    if ((rc = ensure(&c->d_rg_ostatus, &c->rg_ostatus_bytes, sb))) return rc;
+    hipError_t e = xcopy_async(c->d_dist, static_cast<const char *>(dist) + (size_t)plan.ext_lo * vbytes, db,
+                               hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hip_err(e);
+    rc = ragged_locked(c, c->d_dist, vbytes, plan, plan.ext_lo, c->d_cost, c->d_tour, tour_stride, c->d_rg_ostatus,
+                       c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // (the caller's dist may go once this returns)
+        return rc;
+    }
+    e = xcopy_async(cost_out, c->d_cost, cb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = xcopy_async(tour_out, c->d_tour, tb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = xcopy_async(status_out, c->d_rg_ostatus, sb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return hip_err(e);
 }
 
 }  // extern "C"

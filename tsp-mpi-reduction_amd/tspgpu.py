@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = (
     "tspgpu_solve_instance", "tspgpu_solve_instance_i32", "tspgpu_wide_last_dtype",
     # K1 on integer distances
     "tspgpu_validate_i32", "tspgpu_solve_blocks_i32", "tspgpu_solve_blocks_i32_device",
+    # ragged batches (blocks of different sizes, validated per block on the device)
+    "tspgpu_solve_ragged", "tspgpu_solve_ragged_device",
     # tuning / test knobs
     "tspgpu_tuning_set", "tspgpu_tuning_clear",
 )
@@ -117,6 +119,10 @@ def lib():
         L.tspgpu_validate_i32.argtypes = [ip, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.tspgpu_solve_blocks_i32.argtypes = [vp, ip, ctypes.c_int, ctypes.c_int, ip, ip]
         L.tspgpu_solve_blocks_i32_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        L.tspgpu_solve_ragged.argtypes = [vp, vp, ctypes.c_int, i64p, ip, ctypes.c_int, vp, ip, ctypes.c_int, ip]
+        L.tspgpu_solve_ragged_device.argtypes = [vp, vp, ctypes.c_int, i64p, ip, ctypes.c_int, vp, vp, ctypes.c_int,
+                                                 vp, vp]
         L.tspgpu_solve.argtypes = [dp, ctypes.c_int, ctypes.c_int, dp, ip, ctypes.POINTER(Opts)]
         L.tspgpu_last_grid.argtypes = [vp]
         L.tspgpu_last_variant.argtypes = [vp]
@@ -354,6 +360,70 @@ class Context:
                                               stream_ptr)
         if rc:
             raise TspGpuError(rc, "tspgpu_solve_blocks_device")
+
+    def solve_ragged(self, mats, tour_stride: int | None = None):
+        """Blocks of different sizes in one call (tspgpu_solve_ragged), each
+        validated on the device.  mats: a sequence of square arrays, all
+        float64 (or convertible) or all int32 -> (cost (B,) float64 / int32,
+        tours (B, max n + 1) int32 padded with -1, status (B,) int32).  Status
+        0: cost and tour as solve_blocks / solve_blocks_i32 give them; else a
+        negative errno, cost NaN / -1 and the tour row all -1."""
+        mats = [np.asarray(m) for m in mats]
+        integer = bool(mats) and all(np.issubdtype(m.dtype, np.integer) for m in mats)
+        dt = np.int32 if integer else np.float64
+        for m in mats:
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError(f"solve_ragged: a block of shape {m.shape} is not square")
+        ns = np.array([m.shape[0] for m in mats], dtype=np.int32)
+        sizes = ns.astype(np.int64) ** 2
+        offset = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64) if len(mats) else np.zeros(0, np.int64)
+        flat = np.concatenate([np.ascontiguousarray(m, dtype=dt).ravel() for m in mats]) if mats else np.zeros(0, dt)
+        return self.solve_ragged_flat(flat, offset, ns, tour_stride)
+
+    def solve_ragged_flat(self, dist: np.ndarray, offset, n, tour_stride: int | None = None, out=None):
+        """tspgpu_solve_ragged on a flat float64 / int32 array: block b is the
+        n[b] x n[b] matrix at element offset[b] (any order, gaps and overlaps
+        allowed).  tour_stride None: (largest n in 2..20) + 1.  out: optional
+        (cost, tours, status) arrays to write into.  -> (cost, tours, status)."""
+        dist = np.ascontiguousarray(dist)
+        if dist.dtype != np.int32:
+            dist = np.ascontiguousarray(dist, dtype=np.float64)
+        dtype = I32 if dist.dtype == np.int32 else F64
+        offset = np.ascontiguousarray(offset, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        B = len(n)
+        assert len(offset) == B
+        if tour_stride is None:
+            ok = n[(n >= 2) & (n <= MAX_CITIES)]
+            tour_stride = int(ok.max()) + 1 if ok.size else 1
+        if out is None:
+            cost = np.zeros(B, dtype=dist.dtype)
+            tour = np.full((B, tour_stride), -1, dtype=np.int32)
+            status = np.zeros(B, dtype=np.int32)
+        else:
+            cost, tour, status = out
+            assert cost.dtype == dist.dtype and tour.dtype == np.int32 and status.dtype == np.int32
+            assert cost.shape == (B,) and tour.shape == (B, tour_stride) and status.shape == (B,)
+            assert cost.flags.c_contiguous and tour.flags.c_contiguous and status.flags.c_contiguous
+        rc = lib().tspgpu_solve_ragged(self.handle, dist.ctypes.data, dtype, offset.ctypes.data_as(
+            ctypes.POINTER(ctypes.c_int64)), _ip(n), B, cost.ctypes.data, _ip(tour), tour_stride, _ip(status))
+        if rc:
+            raise TspGpuError(rc, "tspgpu_solve_ragged")
+        return cost, tour, status
+
+    def solve_ragged_device(self, d_dist_ptr: int, dtype: int, offset, n, d_cost_ptr: int, d_tour_ptr: int,
+                            tour_stride: int, d_status_ptr: int, stream_ptr: int = 0):
+        """tspgpu_solve_ragged_device: device pointers for dist / cost / tour
+        (B x tour_stride) / status; offset and n are host arrays (read before
+        this returns).  Asynchronous on stream_ptr."""
+        offset = np.ascontiguousarray(offset, dtype=np.int64)
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        assert len(offset) == len(n)
+        rc = lib().tspgpu_solve_ragged_device(self.handle, d_dist_ptr, dtype, offset.ctypes.data_as(
+            ctypes.POINTER(ctypes.c_int64)), _ip(n), len(n), d_cost_ptr, d_tour_ptr, tour_stride, d_status_ptr,
+            stream_ptr)
+        if rc:
+            raise TspGpuError(rc, "tspgpu_solve_ragged_device")
 
     def last_grid(self) -> int:
         return lib().tspgpu_last_grid(self.handle)
