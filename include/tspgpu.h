@@ -89,7 +89,8 @@ int tspgpu_ctx_destroy(tspgpu_ctx *ctx);
 int tspgpu_solve_blocks(tspgpu_ctx *ctx, const double *dist, int n, int nblocks, double *cost_out,
                         int32_t *tour_out);
 
-/* Same, from cities (distance matrix computed on the host, then solved). */
+/* Same, from cities (distance matrix computed on the host, then solved;
+ * tspgpu_solve_cities_upload below builds it on the device instead). */
 int tspgpu_solve_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, int nblocks, double *cost_out,
                         int32_t *tour_out);
 
@@ -172,6 +173,50 @@ int tspgpu_solve_ragged_device(tspgpu_ctx *ctx, const void *d_dist, int dtype, c
  * cost, tour and status back. */
 int tspgpu_solve_ragged(tspgpu_ctx *ctx, const void *dist, int dtype, const int64_t *offset, const int32_t *n,
                         int nblocks, void *cost_out, int32_t *tour_out, int tour_stride, int32_t *status_out);
+
+/* ---------------------------------------------------------------------------
+ * Distances on the device: the entry points above that start from cities
+ * build the matrices on the host (glibc pow, two calls per entry) and upload
+ * them.  These start from cities in device memory and leave the matrices
+ * there, with the bits of tspgpu_distance_matrix: the device squares every
+ * coordinate difference itself and lists the ~10% of squares that lie close
+ * enough to a rounding midpoint for glibc's pow(x, 2) to differ from x*x; the
+ * host runs pow on the listed operands only.  A non-finite
+ * coordinate gives the NaN or infinite entries the host gives (a NaN's
+ * payload aside), so such a block fails validation as it does there.
+ *
+ * d_cities: nblocks*n tspgpu_city (device).  Call-level errors (nothing is
+ * launched): -EINVAL for a NULL context, a NULL pointer with nblocks > 0,
+ * nblocks < 0 or n out of range; nblocks == 0 returns 0.  The fix-up list and
+ * the matrices of the solve forms are the context's, grown on demand and
+ * ordered against other work on the context like the K1 workspace.
+ * ------------------------------------------------------------------------- */
+/* computeDistanceMatrix into d_dist (nblocks*n*n doubles, device), n in
+ * [1, TSPGPU_MAX_CITIES].  NOT fully asynchronous: the call synchronises
+ * `hip_stream` once (after the build kernel, to run the host's pow; once more
+ * in the rare case that the fix-up list overflowed and the build is repeated
+ * with a larger one); the last two kernels are left running on the stream. */
+int tspgpu_distance_matrix_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
+                                  void *hip_stream);
+/* The matrices into a context buffer, then tspgpu_solve_ragged_device with
+ * this n for every block: validation, d_status (nblocks int32), the NaN cost
+ * and the row of -1 of a bad block are the ragged contract.  d_tour: rows of
+ * n+1 entries.  n in [2, TSPGPU_MAX_CITIES] (strict: 16).  Synchronises the
+ * stream as tspgpu_distance_matrix_device does; the solve is left running. */
+int tspgpu_solve_cities_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, int n, int nblocks, double *d_cost,
+                               int32_t *d_tour, int32_t *d_status, void *hip_stream);
+/* tspgpu_solve_cities with the cities uploaded instead of the matrices;
+ * synchronous, same outputs.  Return codes are tspgpu_solve_cities': the
+ * first bad block's code (-EINVAL, -ERANGE) fails the call. */
+int tspgpu_solve_cities_upload(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, int nblocks, double *cost_out,
+                               int32_t *tour_out);
+/* The context's last device build, for tests and measurement: squares
+ * computed (2 per unordered pair), squares sent to the host's pow, build
+ * passes (2: the list overflowed once); and the host's wall time from the
+ * first build launch to the end of its synchronisation (build kernel + the
+ * copy of the list) and of the pow calls.  Any output pointer may be NULL. */
+int tspgpu_cities_last_fixups(const tspgpu_ctx *ctx, uint64_t *squares, uint64_t *flagged, int *build_passes);
+int tspgpu_cities_last_phase_ms(const tspgpu_ctx *ctx, double *build_ms, double *pow_ms);
 
 /* Context-free convenience form (uses a per-thread default context on the
  * current device, created on first use). */
@@ -492,7 +537,7 @@ int tspgpu_reduce(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double
  * TWO_EDGE, CHAIN, LAGRANGE, MST, MST_MINREM, TAIL_CAP_LOG2, EXPAND_LOG2,
  * BUDGET, TIE, PAGEABLE, TAILS, CHAIN_CAP_LOG2, CHAIN_POISON, DEBUG, DEPTH,
  * RECORD_CAP}, CHAIN_FPB, CHAIN_GRID, ENUM_KERNEL, ENUM_WG_PER_CU,
- * HEURISTIC_THREADS, HEURISTIC_ALL_STARTS (csrc/tuning.cpp).
+ * HEURISTIC_THREADS, HEURISTIC_ALL_STARTS, DIST_FIX_CAP (csrc/tuning.cpp).
  * ------------------------------------------------------------------------- */
 /* 0, -ENOENT (no such knob) or -EINVAL (not finite) */
 int tspgpu_tuning_set(const char *name, double value);

@@ -78,6 +78,29 @@ struct tspgpu_ctx {
     size_t h_rg_desc_bytes = 0;
     hipEvent_t ev_rg_desc = nullptr;
     bool rg_desc_pending = false;
+    // Device distance build (tspgpu_distance_matrix_device, cities.h): the
+    // fix-up list (slots; operands, overwritten by the host's pow results),
+    // its counter, the pinned buffers the operands come down to and the
+    // results go up from, the matrices of the solve forms and the upload
+    // form's cities.  Per context
+    // and under the K1 ordering rule (ev_k1_done behind the finish kernel).
+    int64_t *d_ct_slot = nullptr;
+    size_t ct_slot_bytes = 0;
+    double *d_ct_dx = nullptr;
+    size_t ct_dx_bytes = 0;
+    unsigned long long *d_ct_count = nullptr;
+    size_t ct_count_bytes = 0;
+    double *d_ct_dist = nullptr;
+    size_t ct_dist_bytes = 0;
+    tspgpu_city *d_ct_cities = nullptr;
+    size_t ct_cities_bytes = 0;
+    double *h_ct_fix = nullptr;              // pinned
+    size_t h_ct_fix_bytes = 0;
+    unsigned long long *h_ct_count = nullptr;  // pinned
+    // the last build (tspgpu_cities_last_fixups, tspgpu_cities_last_phase_ms)
+    unsigned long long ct_squares = 0, ct_flagged = 0;
+    int ct_passes = 0;
+    double ct_build_ms = 0.0, ct_pow_ms = 0.0;
     char name[256] = {0};
     std::mutex mu;
     // K1-wide per-context cache (buffers of the last (n, value type)), hkwide_impl.h

@@ -3,8 +3,10 @@
 //
 // Replaces the reference's `BlockSolution tsp(vector<City>)` (tsp.cpp:405-509)
 // for a whole batch of blocks in one call.  The distance matrix stays on the
-// host (computeDistanceMatrix, assignment2.h:184-200) because glibc pow(x,2)
-// differs from x*x in ~0.08% of inputs; the device never recomputes it.
+// host (computeDistanceMatrix, assignment2.h:184-200) by default because glibc
+// pow(x,2) differs from x*x in ~0.08% of inputs; the device forms
+// (tspgpu_distance_matrix_device, the end of this file) send the host only
+// the squares where it can differ.
 #include "tspgpu.h"
 #include "tuning.h"
 
@@ -12,6 +14,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -22,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "cities.h"
 #include "ctx.h"
 #include "heldkarp.h"
 #include "k1_cfg.h"
@@ -85,6 +89,12 @@ using namespace tspgpu;
 
 
 namespace {
+
+// glibc's pow and sqrt really called (volatile pointers keep the compiler from
+// folding pow(x, 2) to x*x): tspgpu_distance_matrix and the device build's
+// fix-ups share them
+double (*volatile pow_fn)(double, double) = ::pow;
+double (*volatile sqrt_fn)(double) = ::sqrt;
 
 int hip_err(hipError_t e)
 {
@@ -473,9 +483,7 @@ double tspgpu_table_bytes_per_block(int n)
 int tspgpu_distance_matrix(const tspgpu_city *cities, int n, int nblocks, double *dist)
 {
     // assignment2.h:196: sqrt(pow(dx, 2) + pow(dy, 2)), glibc pow really called
-    // (a volatile pointer keeps the compiler from folding pow(x,2) to x*x).
-    static double (*volatile pow_fn)(double, double) = ::pow;
-    static double (*volatile sqrt_fn)(double) = ::sqrt;
+    // (pow_fn, above)
     if (n < 1 || nblocks < 0 || (nblocks > 0 && (!cities || !dist))) return -EINVAL;
     auto run = [&](int b0, int b1) {
         for (int b = b0; b < b1; ++b) {
@@ -619,6 +627,11 @@ void tspgpu_ctx_release(tspgpu_ctx *c)
     for (void *p : {c->d_rg_desc, c->d_rg_dist, c->d_rg_cost, (void *)c->d_rg_tour, (void *)c->d_rg_status,
                     (void *)c->d_rg_ostatus})
         if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->d_ct_slot, (void *)c->d_ct_dx, (void *)c->d_ct_count,
+                    (void *)c->d_ct_dist, (void *)c->d_ct_cities})
+        if (p) (void)hipFree(p);
+    if (c->h_ct_fix) (void)hipHostFree(c->h_ct_fix);
+    if (c->h_ct_count) (void)hipHostFree(c->h_ct_count);
     if (c->h_rg_desc) (void)hipHostFree(c->h_rg_desc);
     if (c->ev_rg_desc) (void)hipEventDestroy(c->ev_rg_desc);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
@@ -1039,6 +1052,219 @@ int tspgpu_solve_ragged(tspgpu_ctx *c, const void *dist, int dtype, const int64_
     if (e == hipSuccess) e = xcopy_async(status_out, c->d_rg_ostatus, sb, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return hip_err(e);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Distances on the device: cities in HBM -> the reference's
+// matrices, bit for bit.  Build kernel (x*x everywhere, the squares where
+// glibc's pow may differ listed) -> one synchronisation, the host's pow on the
+// listed operands -> patch + finish kernels (cities.hip, dist_exact.h).
+// ---------------------------------------------------------------------------
+namespace {
+
+int cities_args(const tspgpu_ctx *c, const void *cities, int n, int min_n, int nblocks)
+{
+    if (!c || n < min_n || n > TSPGPU_MAX_CITIES || nblocks < 0) return -EINVAL;
+    if (nblocks > 0 && !cities) return -EINVAL;
+    return 0;
+}
+
+// The matrices of nblocks blocks of n cities into d_dist on `stream` (c->mu
+// held).  Synchronises the stream once per build pass; the patch and finish
+// kernels are left running.
+int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
+                        hipStream_t stream)
+{
+    using clk = std::chrono::steady_clock;
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    const unsigned long long squares = (unsigned long long)nblocks * n * (n - 1);
+    // list capacity: a quarter of the squares (the rule flags a tenth of the
+    // generator's), or the test knob; an overflowing build is run again
+    unsigned long long cap = squares / 4;
+    double kv = 0.0;
+    if (tspgpu::tuned("DIST_FIX_CAP", &kv) && kv >= 1.0) cap = (unsigned long long)kv;
+    if (cap > squares) cap = squares;
+    if (cap < 1) cap = 1;
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    if ((rc = ensure(&c->d_ct_count, &c->ct_count_bytes, sizeof(unsigned long long)))) return rc;
+    if (!c->h_ct_count && (e = hipHostMalloc((void **)&c->h_ct_count, sizeof(unsigned long long),
+                                             hipHostMallocDefault)) != hipSuccess) {
+        c->h_ct_count = nullptr;
+        return hip_err(e);
+    }
+    if (!c->ev_k1_done && (e = hipEventCreateWithFlags(&c->ev_k1_done, hipEventDisableTiming)) != hipSuccess)
+        return hip_err(e);
+    // the list and the pinned buffers are the context's: behind the previous
+    // K1, ragged or build launch when that ran on another stream
+    if (c->k1_launched && stream != c->k1_last_stream) {
+        if ((e = hipStreamWaitEvent(stream, c->ev_k1_done, 0)) != hipSuccess) return hip_err(e);
+    }
+    const auto t0 = clk::now();
+    unsigned long long count = 0;
+    int passes = 0;
+    for (;;) {
+        const size_t lb = (size_t)cap * sizeof(double);
+        if ((rc = ensure(&c->d_ct_slot, &c->ct_slot_bytes, (size_t)cap * sizeof(int64_t)))) return rc;
+        if ((rc = ensure(&c->d_ct_dx, &c->ct_dx_bytes, lb))) return rc;
+        if (c->h_ct_fix_bytes < lb) {
+            // (growing: an earlier build's copy of its results, on another
+            // stream, may still be reading the old buffer)
+            if (c->h_ct_fix && (e = hipDeviceSynchronize()) != hipSuccess) return hip_err(e);
+            if (c->h_ct_fix) (void)hipHostFree(c->h_ct_fix);
+            c->h_ct_fix = nullptr;
+            c->h_ct_fix_bytes = 0;
+            if ((e = hipHostMalloc((void **)&c->h_ct_fix, lb, hipHostMallocDefault)) != hipSuccess) {
+                c->h_ct_fix = nullptr;
+                return hip_err(e);
+            }
+            c->h_ct_fix_bytes = lb;
+        }
+        e = hipMemsetAsync(c->d_ct_count, 0, sizeof(unsigned long long), stream);
+        if (e == hipSuccess)
+            e = launch_cities_build(d_cities, n, nblocks, d_dist, c->d_ct_slot, c->d_ct_dx, cap, c->d_ct_count, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(c->h_ct_count, c->d_ct_count, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_ct_fix, c->d_ct_dx, lb, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return hip_err(e);
+        ++passes;
+        count = *c->h_ct_count;
+        if (count <= cap) break;
+        if (passes >= 2 || count > squares) return -EIO;  // (the build is deterministic: the second pass fits)
+        cap = count;
+    }
+    const auto t1 = clk::now();
+    // the host's pow on the flagged operands, in place, on up to 16 threads
+    // like tspgpu_distance_matrix
+    double *v = c->h_ct_fix;
+    auto run = [v](size_t a, size_t b) {
+        for (size_t t = a; t < b; ++t) v[t] = pow_fn(v[t], 2);
+    };
+    int nt = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
+    if (count < (1u << 16)) nt = 1;
+    if (nt <= 1) {
+        run(0, (size_t)count);
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t) th.emplace_back(run, (size_t)(count * t / nt), (size_t)(count * (t + 1) / nt));
+        for (auto &x : th) x.join();
+    }
+    const auto t2 = clk::now();
+    if (count)
+        e = hipMemcpyAsync(c->d_ct_dx, v, (size_t)count * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = launch_cities_patch(d_dist, c->d_ct_slot, c->d_ct_dx, count, stream);
+    if (e == hipSuccess) e = launch_cities_finish(n, nblocks, d_dist, stream);
+    if (e == hipSuccess) e = hipEventRecord(c->ev_k1_done, stream);
+    if (e != hipSuccess) return hip_err(e);
+    c->k1_last_stream = stream;
+    c->k1_launched = true;
+    c->ct_squares = squares;
+    c->ct_flagged = count;
+    c->ct_passes = passes;
+    c->ct_build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->ct_pow_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return 0;
+}
+
+// build into the context's matrices, then the ragged path with one n for
+// every block (c->mu held)
+int cities_solve_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_cost,
+                        int32_t *d_tour, int32_t *d_status, hipStream_t stream)
+{
+    std::vector<int64_t> offset((size_t)nblocks);
+    std::vector<int32_t> ns((size_t)nblocks, n);
+    for (int b = 0; b < nblocks; ++b) offset[b] = (int64_t)b * n * n;
+    RaggedPlan plan;
+    int rc = ragged_plan(ns.data(), offset.data(), nblocks, c->strict, 8, &plan);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    if ((rc = ensure(&c->d_ct_dist, &c->ct_dist_bytes, (size_t)nblocks * n * n * sizeof(double)))) return rc;
+    if ((rc = cities_build_locked(c, d_cities, n, nblocks, c->d_ct_dist, stream))) return rc;
+    return ragged_locked(c, c->d_ct_dist, 8, plan, 0, d_cost, d_tour, n + 1, d_status, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tspgpu_distance_matrix_device(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
+                                  void *hip_stream)
+{
+    const int rc = cities_args(c, d_cities, n, 1, nblocks);
+    if (rc) return rc;
+    if (nblocks == 0) return 0;
+    if (!d_dist) return -EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return cities_build_locked(c, d_cities, n, nblocks, d_dist, (hipStream_t)hip_stream);
+}
+
+int tspgpu_solve_cities_device(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_cost,
+                               int32_t *d_tour, int32_t *d_status, void *hip_stream)
+{
+    int rc = cities_args(c, d_cities, n, 2, nblocks);
+    if (!rc) rc = check_n(n, c->strict);
+    if (rc) return rc;
+    if (nblocks == 0) return 0;
+    if (!d_cost || !d_tour || !d_status) return -EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return cities_solve_locked(c, d_cities, n, nblocks, d_cost, d_tour, d_status, (hipStream_t)hip_stream);
+}
+
+int tspgpu_solve_cities_upload(tspgpu_ctx *c, const tspgpu_city *cities, int n, int nblocks, double *cost_out,
+                               int32_t *tour_out)
+{
+    int rc = cities_args(c, cities, n, 2, nblocks);
+    if (!rc) rc = check_n(n, c->strict);
+    if (rc) return rc;
+    if (nblocks == 0) return 0;
+    if (!cost_out || !tour_out) return -EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    const size_t ib = (size_t)nblocks * n * sizeof(tspgpu_city);
+    const size_t cb = (size_t)nblocks * sizeof(double);
+    const size_t tb = (size_t)nblocks * (n + 1) * sizeof(int32_t);
+    const size_t sb = (size_t)nblocks * sizeof(int32_t);
+    if ((rc = ensure(&c->d_ct_cities, &c->ct_cities_bytes, ib))) return rc;
+    if ((rc = ensure(&c->d_cost, &c->cost_bytes, cb))) return rc;
+    if ((rc = ensure(&c->d_tour, &c->tour_bytes, tb))) return rc;
+    if ((rc = ensure(&c->d_rg_ostatus, &c->rg_ostatus_bytes, sb))) return rc;
+    hipError_t e = xcopy_async(c->d_ct_cities, cities, ib, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hip_err(e);
+    rc = cities_solve_locked(c, c->d_ct_cities, n, nblocks, c->d_cost, c->d_tour, c->d_rg_ostatus, c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // (the caller's cities may go once this returns)
+        return rc;
+    }
+    std::vector<int32_t> status((size_t)nblocks);
+    e = xcopy_async(cost_out, c->d_cost, cb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = xcopy_async(tour_out, c->d_tour, tb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = xcopy_async(status.data(), c->d_rg_ostatus, sb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_err(e);
+    for (int b = 0; b < nblocks; ++b)
+        if (status[b]) return status[b];  // the first bad block's code, as tspgpu_solve_cities
+    return 0;
+}
+
+int tspgpu_cities_last_fixups(const tspgpu_ctx *c, uint64_t *squares, uint64_t *flagged, int *build_passes)
+{
+    if (!c) return -EINVAL;
+    if (squares) *squares = c->ct_squares;
+    if (flagged) *flagged = c->ct_flagged;
+    if (build_passes) *build_passes = c->ct_passes;
+    return 0;
+}
+
+int tspgpu_cities_last_phase_ms(const tspgpu_ctx *c, double *build_ms, double *pow_ms)
+{
+    if (!c) return -EINVAL;
+    if (build_ms) *build_ms = c->ct_build_ms;
+    if (pow_ms) *pow_ms = c->ct_pow_ms;
+    return 0;
 }
 
 }  // extern "C"

@@ -25,6 +25,8 @@ Knob g_knobs[] = {
     {"WG_PER_CU", false, 0},       // workgroups per CU of the layer kernels
     {"THREADS", false, 0},         // threads per workgroup of the layer kernels
     {"LDS_TABLE_MAX_N", false, 0}, // largest N whose whole table lives in LDS
+    // device distance build (tspgpu.cpp, read at every build)
+    {"DIST_FIX_CAP", false, 0},    // tests: entries of the fix-up list (default a quarter of the squares; below 1 ignored)
     // K1-wide (hkwide.hip)
     {"WIDE_PULL", false, 0},       // 1: per-destination layer form everywhere, 0: row-owner form
     // K2 (search_abi.cpp, read at search creation / run)

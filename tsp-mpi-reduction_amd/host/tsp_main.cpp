@@ -27,6 +27,8 @@
 // replays them on the host instead.
 //
 // TSP_STATS=1 adds one statistics line on stderr (phase times, relaxations/s).
+// TSP_DEVICE_DIST=1 builds the distance matrices on the GPU from uploaded
+// cities (tspgpu_solve_cities_upload) instead of on the host; same output.
 //
 // Deviations (documented in DESIGN.md), all where the reference is undefined:
 // n < 2, numBlocks < 1 or numBlocks < P exit 2 with a message on stderr
@@ -76,8 +78,11 @@ int visible_devices()
 // (keep: the context of device first_dev stays open and is returned, for the
 // merges that follow on it — a second context costs a HIP stream and device
 // queries; null: every context is destroyed)
+// (dist_ms: the distance matrices' share of the wall time, the largest over
+// the GPUs: the host's computeDistanceMatrix, or with TSP_DEVICE_DIST the
+// device build up to the end of the host's pow calls)
 int solve_range(const std::vector<tspgpu_city> &cities, int n, int lo, int count, int gpus, int first_dev,
-                double *cost, int32_t *tour, tspgpu_ctx **keep = nullptr)
+                double *cost, int32_t *tour, tspgpu_ctx **keep = nullptr, double *dist_ms = nullptr)
 {
     const int B = count;
     if (B <= 0) return 0;
@@ -85,6 +90,8 @@ int solve_range(const std::vector<tspgpu_city> &cities, int n, int lo, int count
     if (gpus > B) gpus = B;
     const int ndev = visible_devices();
     std::vector<int> rcs(gpus, 0);
+    std::vector<double> dms(gpus, 0.0);
+    const bool device_dist = env_int("TSP_DEVICE_DIST", 0) != 0;
     std::vector<std::thread> th;
     for (int g = 0; g < gpus; ++g) {
         th.emplace_back([&, g] {
@@ -95,9 +102,21 @@ int solve_range(const std::vector<tspgpu_city> &cities, int n, int lo, int count
             o.strict = 1;
             tspgpu_ctx *ctx = nullptr;
             int rc = tspgpu_ctx_create(&o, &ctx);
-            if (!rc)
-                rc = tspgpu_solve_cities(ctx, cities.data() + (size_t)(lo + a) * n, n, b - a, cost + a,
-                                         tour + (size_t)a * (n + 1));
+            const tspgpu_city *mine = cities.data() + (size_t)(lo + a) * n;
+            if (!rc && device_dist) {
+                rc = tspgpu_solve_cities_upload(ctx, mine, n, b - a, cost + a, tour + (size_t)a * (n + 1));
+                double build_ms = 0.0, pow_ms = 0.0;
+                if (!rc && !tspgpu_cities_last_phase_ms(ctx, &build_ms, &pow_ms)) dms[g] = build_ms + pow_ms;
+            } else if (!rc) {
+                // tspgpu_solve_cities' two steps, apart for the clock
+                timespec t0, t1;
+                clock_gettime(CLOCK_MONOTONIC_RAW, &t0);
+                std::vector<double> dist((size_t)(b - a) * n * n);
+                rc = n < 2 ? -EINVAL : tspgpu_distance_matrix(mine, n, b - a, dist.data());
+                clock_gettime(CLOCK_MONOTONIC_RAW, &t1);
+                dms[g] = 1e3 * (double)(t1.tv_sec - t0.tv_sec) + 1e-6 * (double)(t1.tv_nsec - t0.tv_nsec);
+                if (!rc) rc = tspgpu_solve_blocks(ctx, dist.data(), n, b - a, cost + a, tour + (size_t)a * (n + 1));
+            }
             if (ctx && g == 0 && keep && !rc)
                 *keep = ctx;
             else if (ctx)
@@ -106,6 +125,8 @@ int solve_range(const std::vector<tspgpu_city> &cities, int n, int lo, int count
         });
     }
     for (auto &t : th) t.join();
+    if (dist_ms)
+        for (double v : dms) *dist_ms = v > *dist_ms ? v : *dist_ms;
     for (int rc : rcs)
         if (rc) return rc;
     return 0;
@@ -328,6 +349,7 @@ int main(int argc, char **argv)
     int rc;
     timespec ts_solve0, ts_solve1, ts_merge1;
     tspgpu_ctx *kept = nullptr;  // the block search's context on TSP_GPU, reused by the merges
+    double dist_ms = 0.0;        // the distance matrices' share of the block search (this process's blocks)
     clock_gettime(CLOCK_MONOTONIC_RAW, &ts_solve0);
     // (the HIP runtime's own start-up, the analogue of the reference's
     // MPI_Init inside its clock: reported apart by TSP_STATS)
@@ -342,7 +364,7 @@ int main(int argc, char **argv)
         const uint64_t key = job_key(n, B, X, Y);
         int failed = 0;
         rc = solve_range(cities, n, 0, cnt[0], env_int("TSP_GPUS", 1), env_int("TSP_GPU", 0), cost.data(), tour.data(),
-                         &kept);
+                         &kept, &dist_ms);
         if (!rc) rc = read_rank_files(gather_dir(key), key, P, n, B, X, Y, cnt, off, cost.data(), tour.data(), &failed);
         if (rc && failed) {
             std::fflush(stdout);
@@ -351,7 +373,7 @@ int main(int argc, char **argv)
         }
     } else {
         rc = solve_range(cities, n, 0, B, env_int("TSP_GPUS", 1), env_int("TSP_GPU", 0), cost.data(), tour.data(),
-                         &kept);
+                         &kept, &dist_ms);
     }
     if (rc) {
         std::fflush(stdout);
@@ -413,8 +435,10 @@ int main(int argc, char **argv)
         const double relax = tspgpu_relaxations_per_block(n) * (multi ? 0.0 : (double)B);
         std::fprintf(stderr,
                      "tsp stats: n %d blocks %d ranks %d | setup %.3f ms, block search %.3f ms (HIP runtime start-up "
-                     "%.3f ms of it; %s), merge %.3f ms, total %.3f ms | %.4g DP relaxations/s\n",
-                     n, B, P, 1e3 * sec(start, ts_solve0), 1e3 * solve_s, 1e3 * sec(ts_solve0, ts_rt),
+                     "%.3f ms of it, distances %.3f ms of it on the %s; %s), merge %.3f ms, total %.3f ms | %.4g DP "
+                     "relaxations/s\n",
+                     n, B, P, 1e3 * sec(start, ts_solve0), 1e3 * solve_s, 1e3 * sec(ts_solve0, ts_rt), dist_ms,
+                     env_int("TSP_DEVICE_DIST", 0) ? "device" : "host",
                      multi ? "rank 0's share + the rank files" : "all blocks, one process",
                      1e3 * sec(ts_solve1, ts_merge1), 1e3 * sec(start, end),
                      solve_s > 0 && relax > 0 ? relax / solve_s : 0.0);

@@ -48,7 +48,11 @@ std::vector<BlockSolution> tspBatch(const std::vector<std::vector<City>> &blocks
     }
     std::vector<double> cost(B);
     std::vector<int32_t> tour((size_t)B * (n + 1));
-    const int rc = tspgpu_solve_cities(shim_ctx(), flat.data(), n, B, cost.data(), tour.data());
+    // TSP_DEVICE_DIST=1: the distance matrices on the GPU from uploaded cities
+    // (same bits, the host's pow on the flagged squares only)
+    const char *dd = std::getenv("TSP_DEVICE_DIST");
+    const int rc = dd && std::atoi(dd) ? tspgpu_solve_cities_upload(shim_ctx(), flat.data(), n, B, cost.data(), tour.data())
+                                       : tspgpu_solve_cities(shim_ctx(), flat.data(), n, B, cost.data(), tour.data());
     if (rc) {
         std::fprintf(stderr, "tspgpu_solve_cities: %s\n", tspgpu_strerror(rc));
         std::exit(3);

@@ -42,6 +42,9 @@ EXPORTED_SYMBOLS = (
     "tspgpu_validate_i32", "tspgpu_solve_blocks_i32", "tspgpu_solve_blocks_i32_device",
     # ragged batches (blocks of different sizes, validated per block on the device)
     "tspgpu_solve_ragged", "tspgpu_solve_ragged_device",
+    # distances on the device (cities in device memory, the host's pow on the flagged squares only)
+    "tspgpu_distance_matrix_device", "tspgpu_solve_cities_device", "tspgpu_solve_cities_upload",
+    "tspgpu_cities_last_fixups", "tspgpu_cities_last_phase_ms",
     # tuning / test knobs
     "tspgpu_tuning_set", "tspgpu_tuning_clear",
 )
@@ -80,6 +83,11 @@ LEVEL_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_v
 class City(ctypes.Structure):
     """tspgpu_city == the reference's City (assignment2.h:13-18)."""
     _fields_ = [("id", ctypes.c_int32), ("x", ctypes.c_double), ("y", ctypes.c_double)]
+
+
+# the same 24 bytes for numpy: np.frombuffer(city_array, CITY_DTYPE), Context.upload(...)
+CITY_DTYPE = np.dtype([("id", "<i4"), ("x", "<f8"), ("y", "<f8")], align=True)
+assert CITY_DTYPE.itemsize == ctypes.sizeof(City) == 24
 
 
 class Opts(ctypes.Structure):
@@ -123,6 +131,12 @@ def lib():
         L.tspgpu_solve_ragged.argtypes = [vp, vp, ctypes.c_int, i64p, ip, ctypes.c_int, vp, ip, ctypes.c_int, ip]
         L.tspgpu_solve_ragged_device.argtypes = [vp, vp, ctypes.c_int, i64p, ip, ctypes.c_int, vp, vp, ctypes.c_int,
                                                  vp, vp]
+        L.tspgpu_distance_matrix_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.tspgpu_solve_cities_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+        L.tspgpu_solve_cities_upload.argtypes = [vp, ctypes.POINTER(City), ctypes.c_int, ctypes.c_int, dp, ip]
+        L.tspgpu_cities_last_fixups.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_int)]
+        L.tspgpu_cities_last_phase_ms.argtypes = [vp, dp, dp]
         L.tspgpu_solve.argtypes = [dp, ctypes.c_int, ctypes.c_int, dp, ip, ctypes.POINTER(Opts)]
         L.tspgpu_last_grid.argtypes = [vp]
         L.tspgpu_last_variant.argtypes = [vp]
@@ -345,14 +359,52 @@ class Context:
         if rc:
             raise TspGpuError(rc, "tspgpu_solve_blocks_i32_device")
 
-    def solve_cities(self, blocks):
-        arr, n, B = cities_array(blocks)
+    def solve_cities(self, blocks, device_dist: bool = False):
+        """blocks: lists of (id, x, y), or a (ctypes City array, n, B) triple ->
+        (costs, tours).  device_dist: upload the cities and build the matrices
+        on the device (tspgpu_solve_cities_upload) instead of on the host."""
+        arr, n, B = blocks if isinstance(blocks, tuple) else cities_array(blocks)
         cost = np.zeros(B, dtype=np.float64)
         tour = np.full((B, n + 1), -1, dtype=np.int32)
-        rc = lib().tspgpu_solve_cities(self.handle, arr, n, B, _dp(cost), _ip(tour))
+        fn, what = ((lib().tspgpu_solve_cities_upload, "tspgpu_solve_cities_upload") if device_dist else
+                    (lib().tspgpu_solve_cities, "tspgpu_solve_cities"))
+        rc = fn(self.handle, arr, n, B, _dp(cost), _ip(tour))
         if rc:
-            raise TspGpuError(rc, "tspgpu_solve_cities")
+            raise TspGpuError(rc, what)
         return cost, tour
+
+    def distance_matrix_device(self, d_cities_ptr: int, n: int, nblocks: int, d_dist_ptr: int, stream_ptr: int = 0):
+        """tspgpu_distance_matrix_device: nblocks*n City structs at d_cities_ptr
+        -> nblocks*n*n float64 at d_dist_ptr, the bits of distance_matrix().
+        Synchronises the stream once; the last kernels are left running."""
+        rc = lib().tspgpu_distance_matrix_device(self.handle, d_cities_ptr, n, nblocks, d_dist_ptr, stream_ptr)
+        if rc:
+            raise TspGpuError(rc, "tspgpu_distance_matrix_device")
+
+    def solve_cities_device(self, d_cities_ptr: int, n: int, nblocks: int, d_cost_ptr: int, d_tour_ptr: int,
+                            d_status_ptr: int, stream_ptr: int = 0):
+        """tspgpu_solve_cities_device: cities on the device -> cost (B float64),
+        tours (B x (n+1) int32) and status (B int32) on the device, under the
+        ragged contract (a bad block: its status, NaN, a row of -1)."""
+        rc = lib().tspgpu_solve_cities_device(self.handle, d_cities_ptr, n, nblocks, d_cost_ptr, d_tour_ptr,
+                                              d_status_ptr, stream_ptr)
+        if rc:
+            raise TspGpuError(rc, "tspgpu_solve_cities_device")
+
+    def cities_last_fixups(self):
+        """(squares, flagged, build_passes) of this context's last device distance build."""
+        sq, fl, ps = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        self._check(lib().tspgpu_cities_last_fixups(self.handle, ctypes.byref(sq), ctypes.byref(fl),
+                                                    ctypes.byref(ps)), "tspgpu_cities_last_fixups")
+        return sq.value, fl.value, ps.value
+
+    def cities_last_phase_ms(self):
+        """(build_ms, pow_ms): host wall time of the last build's kernel + list
+        copy + synchronisation, and of its pow calls."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        self._check(lib().tspgpu_cities_last_phase_ms(self.handle, ctypes.byref(a), ctypes.byref(b)),
+                    "tspgpu_cities_last_phase_ms")
+        return a.value, b.value
 
     def solve_device(self, d_dist_ptr: int, n: int, nblocks: int, d_cost_ptr: int, d_tour_ptr: int,
                      stream_ptr: int = 0):
