@@ -21,6 +21,7 @@
  *   -EIO     a HIP runtime call or kernel launch failed
  *   -EDEADLK (K3) the reference's mergeBlocks would never terminate for these paths
  *            (its rotation loop, tsp.cpp:236-239, looks for a city that is not there)
+ *   -ENOSPC  (K3) the merged tour is longer than path_cap (everything else was written)
  *   -EOVERFLOW (K2) more optimal tours than can be enumerated, n > 31
  */
 #ifndef TSPGPU_H
@@ -524,6 +525,51 @@ int tspgpu_merge(tspgpu_ctx *ctx, const tspgpu_city *p1, int L1, double c1, cons
  * to receive %i cities from process %i" lines (tsp.cpp:88) into log. */
 int tspgpu_reduce(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
                   double *final_cost, char *log, int logcap);
+/* tspgpu_reduce, and the merged tour: rank 0's final path (cities, closing
+ * city included; with nprocs > 1 the reference's stale receive lists can
+ * repeat cities, so the length is data-dependent).  *path_len is always set
+ * to the full length; path_out receives min(len, path_cap) cities; a short
+ * path_cap returns -ENOSPC after final_cost, log and *path_len are written.
+ * path_out may be NULL with path_cap 0 (length query).  -EINVAL also for a
+ * NULL path_len, path_cap < 0, or a NULL path_out with path_cap > 0. */
+int tspgpu_reduce_path(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks,
+                       int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log,
+                       int logcap);
+/* The same from K1's device outputs, without a visit to the host: d_cities
+ * (nblocks*n), d_tour (rows of n+1), d_cost (nblocks doubles), d_status
+ * (nblocks int32, or NULL: the caller guarantees every block is valid) are
+ * device pointers on the context's device, produced on hip_stream; the
+ * reduce runs on the context's stream after an event wait on hip_stream.
+ * d_path_out: device, path_cap cities (may be NULL with path_cap 0).
+ * Synchronous (the merge needs host decisions).  One device pass gathers the
+ * block paths (convPathToCityPath, assignment2.h:76-84) and takes the facts
+ * tspgpu_reduce scans its host paths for — exact coordinate extrema, so the
+ * candidate window is bit-equal to tspgpu_reduce's — and only the nblocks
+ * costs come to the host (the cost fold stays there, in merge order, with
+ * glibc).  A non-zero status fails the call with the first such block's code
+ * before anything is merged (d_path_out untouched; such a block's tour row
+ * is never read); a tour entry outside [0, n) under status 0 -> -EINVAL
+ * (checked before it indexes anything); non-finite coordinates -> -EINVAL;
+ * -EDEADLK as tspgpu_reduce.  n in [2, TSPGPU_MAX_CITIES], nblocks * (n+1)
+ * <= INT_MAX.  Same cost, log and path as tspgpu_reduce_path on the gathered
+ * paths for any input; ids spread wider than 8 * nblocks * (n+1) are not
+ * checked for uniqueness on the device and take the general per-merge path
+ * where the host form may take the one-kernel folds (same answer, slower). */
+int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *d_tour, const double *d_cost,
+                         const int32_t *d_status, int n, int nblocks, int nprocs, double *final_cost,
+                         tspgpu_city *d_path_out, int path_cap, int *path_len, char *log, int logcap,
+                         void *hip_stream);
+/* Device time of the context's last tspgpu_reduce_device's gather, summary
+ * and uniqueness kernels (HIP events); a measurement aid. */
+int tspgpu_reduce_device_last_ms(const tspgpu_ctx *ctx, double *gather_ms);
+/* Cities on the host in, final cost / merged tour / log out: uploads the
+ * cities, tspgpu_solve_cities_device, tspgpu_reduce_device, one copy of the
+ * path back.  Buffers are per call.  Return codes: tspgpu_solve_cities_upload's
+ * for the block search (the first bad block's code), tspgpu_reduce_path's for
+ * the merge. */
+int tspgpu_pipeline_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, int nblocks, int nprocs,
+                           double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log,
+                           int logcap);
 
 /* ---------------------------------------------------------------------------
  * Tuning and test knobs.  The defaults are the measured best; a knob changes

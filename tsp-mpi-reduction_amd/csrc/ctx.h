@@ -101,6 +101,10 @@ struct tspgpu_ctx {
     unsigned long long ct_squares = 0, ct_flagged = 0;
     int ct_passes = 0;
     double ct_build_ms = 0.0, ct_pow_ms = 0.0;
+    // the last tspgpu_reduce_device's gather + summary + uniqueness kernels,
+    // from HIP events (tspgpu_reduce_device_last_ms)
+    double k3_gather_ms = 0.0;
+    hipEvent_t ev_k3_gather[2] = {nullptr, nullptr};  // created by the first tspgpu_reduce_device
     char name[256] = {0};
     std::mutex mu;
     // K1-wide per-context cache (buffers of the last (n, value type)), hkwide_impl.h

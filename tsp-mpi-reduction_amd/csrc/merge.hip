@@ -23,6 +23,14 @@
 // If there are more candidates than the buffer holds, the host scans all
 // pairs itself.  The splice is a gather kernel; the first-occurrence searches
 // it needs are atomicMin reductions.  One host round trip per merge.
+//
+// The reduction has one core and two fronts.  reduce_core
+// works on block paths in device memory and can leave rank 0's final path
+// (the merged tour) in host or device memory.  reduce_host (tspgpu_reduce,
+// tspgpu_reduce_path) scans host paths and uploads them; tspgpu_reduce_device
+// takes K1's outputs where tspgpu_solve_cities_device left them: paths.hip
+// gathers the paths and brings the same facts, so only the costs visit the
+// host.  tspgpu_pipeline_cities chains upload, K1 and that.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +43,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "paths.h"
 #include "xfer.h"
 #include "tuning.h"
 #include "wave.h"
@@ -1003,8 +1012,7 @@ double bbox_diagonal(const tspgpu_city *c, size_t n)
         y0 = std::min(y0, c[i].y);
         y1 = std::max(y1, c[i].y);
     }
-    if (!(x1 >= x0) || !(y1 >= y0)) return 0.0;
-    return std::sqrt((x1 - x0) * (x1 - x0) + (y1 - y0) * (y1 - y0)) * (1.0 + 1e-9) + 1e-300;
+    return tspgpu::path_bbox_diagonal(x0, x1, y0, y1);  // (shared with the device summary: paths_facts.h)
 }
 
 bool finite_cities(const tspgpu_city *c, size_t n)
@@ -1013,6 +1021,180 @@ bool finite_cities(const tspgpu_city *c, size_t n)
         if (!std::isfinite(c[i].x) || !std::isfinite(c[i].y)) return false;
     return true;
 }
+
+void put_log(const std::string &text, char *log, int logcap)
+{
+    if (!log || logcap <= 0) return;
+    const size_t k = std::min(text.size(), (size_t)logcap - 1);
+    std::memcpy(log, text.data(), k);
+    log[k] = 0;
+}
+
+// Where the core leaves rank 0's final path: up to cap cities at p (a host
+// or a device pointer; may be null with cap 0), the full length in *len.
+struct PathDest {
+    tspgpu_city *p;
+    bool device;
+    int cap;
+    int *len;
+};
+
+// The core of the reduction (ctx->mu held, the device set): the distribution
+// counts, every logical rank's left fold and the reduction tree over the
+// block paths at `blocks` (DEVICE memory, nblocks paths of L cities; nblocks
+// >= 2), costs on the host.  dmax: the cities' padded bounding-box diagonal;
+// fold_ok: the paths close on their first city and ids are unique across
+// blocks (the one-kernel fold merges' precondition).  -> *final_cost, the
+// log text, and rank 0's final path into dest (optional).
+int reduce_core(tspgpu_ctx *ctx, const tspgpu_city *blocks, int L, const double *costs, int nblocks, int nprocs,
+                double dmax, bool fold_ok, double *final_cost, std::string &text, const PathDest *dest)
+{
+    const size_t ncity = (size_t)nblocks * L;
+    Merger m;
+    int rc = m.init(ctx, dmax);
+    if (rc) return rc;
+    // distributeBlocks' counts (tsp.cpp:167-192): rank r gets #{b in [1,B] : b mod P == r}
+    std::vector<int> cnt(nprocs, 0);
+    for (int b = nblocks; b > 0; --b) cnt[b % nprocs]++;
+    // Every buffer a queued merge may touch is sized up front (a merged path
+    // never exceeds all cities; a received list never exceeds all cities), so
+    // nothing is reallocated while merges are in flight.
+    std::vector<DVec> rank(nprocs), received(nprocs);
+    DVec tmp;
+    std::vector<double> rcost(nprocs, 0.0);
+    rc = tmp.reserve(ncity, m.st);
+    int next = 0;
+    if (!rc && fold_ok && L <= kFoldL2 && tspgpu::tuned_or("K3_PERSIST", 1) != 0) {
+        // (tuning knob K3_PERSIST = 0: the per-merge launches instead; tests compare both)
+        // every rank's fold in one persistent launch (fold_persist_kernel)
+        rc = persist_folds(m, blocks, L, costs, cnt, rank, tmp, rcost);
+        next = nblocks;
+    }
+    for (int r = 0; r < nprocs && !rc && next < nblocks; ++r) {
+        rc = rank[r].reserve(ncity, m.st);
+        if (rc) break;
+        rc = herr(xcopy_async(rank[r].p, blocks + (size_t)next * L, L * sizeof(tspgpu_city), hipMemcpyDeviceToDevice,
+                              m.st));
+        rank[r].len = L;
+        rcost[r] = costs[next];
+        ++next;
+        // each logical rank folds its contiguous block range left (tsp.cpp:348-352)
+        for (int j = 1; j < cnt[r] && !rc; ++j, ++next)
+            rc = m.merge(rank[r], tmp, &rcost[r], blocks + (size_t)next * L, L, &costs[next], fold_ok);
+    }
+    // MPI_ManualReduce (tsp.cpp:52-134): the receiver appends every received
+    // path to one function-local list and merges with the WHOLE list
+    // (tsp.cpp:67,93-98,115-120)
+    auto receive = [&](int to, int from) -> int {
+        // the copy below reads rank[from]'s final path: every queued merge
+        // (and any stall) must be resolved first
+        int r2 = m.sync();
+        if (r2) return r2;
+        DVec &acc = received[to];
+        const size_t add = rank[from].len;
+        r2 = acc.reserve(std::max(acc.len + add, ncity), m.st);
+        if (r2) return r2;
+        r2 = herr(xcopy_async(acc.p + acc.len, rank[from].p, add * sizeof(tspgpu_city), hipMemcpyDeviceToDevice,
+                                 m.st));
+        if (r2) return r2;
+        acc.len += add;
+        return m.merge(rank[to], tmp, &rcost[to], acc.p, (int)acc.len, &rcost[from]);
+    };
+    const int lastpower = 1 << (int)std::log2((double)nprocs);
+    for (int i = 0; i < nprocs - lastpower && !rc; ++i) {
+        char line[128];
+        std::snprintf(line, sizeof line, "process %i is about to receive %i cities from process %i\n", i,
+                      (int)rank[i + lastpower].len, i + lastpower);  // tsp.cpp:88
+        text += line;
+        rc = receive(i, i + lastpower);
+    }
+    for (int d = 0; d < (int)std::log2((double)lastpower) && !rc; ++d)
+        for (int k = 0; k < lastpower && !rc; k += 1 << (d + 1)) rc = receive(k, k + (1 << d));
+    if (!rc) rc = m.sync();
+    if (!rc && dest) {
+        // rank 0 ends with finalSolution.path (tsp.cpp:355)
+        *dest->len = (int)rank[0].len;
+        const size_t k = std::min(rank[0].len, (size_t)dest->cap);
+        if (k)
+            rc = herr(xcopy_async(dest->p, rank[0].p, k * sizeof(tspgpu_city),
+                                  dest->device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, m.st));
+    }
+    const hipError_t es = hipStreamSynchronize(m.st);
+    if (!rc && dest) rc = herr(es);
+    for (auto &v : rank) v.release();
+    for (auto &v : received) v.release();
+    tmp.release();
+    if (rc) return rc;
+    *final_cost = rcost[0];
+    return 0;
+}
+
+// The one-kernel fold merges need block tours that close on their first city
+// and ids unique across blocks (the reference's generator numbers cities
+// globally); anything else takes the general path.  The host scan.
+bool host_fold_ok(const tspgpu_city *paths, int L, int nblocks)
+{
+    bool fold_ok = L >= 3;
+    if (fold_ok) {
+        std::vector<int> ids;
+        ids.reserve((size_t)nblocks * (L - 1));
+        for (int b = 0; b < nblocks && fold_ok; ++b) {
+            const tspgpu_city *pb = paths + (size_t)b * L;
+            if (pb[0].id != pb[L - 1].id) fold_ok = false;
+            for (int k = 0; k < L - 1; ++k) ids.push_back(pb[k].id);
+        }
+        std::sort(ids.begin(), ids.end());
+        if (fold_ok && std::adjacent_find(ids.begin(), ids.end()) != ids.end()) fold_ok = false;
+    }
+    return fold_ok;
+}
+
+// The host front of tspgpu_reduce / tspgpu_reduce_path: argument checks, the
+// three host scans, the upload, then the core.  dest null: no path wanted.
+int reduce_host(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
+                double *final_cost, const PathDest *dest, char *log, int logcap)
+{
+    if (log && logcap > 0) log[0] = 0;
+    if (!ctx || !paths || !costs || !final_cost) return -EINVAL;
+    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || L < 2) return -EINVAL;
+    if (dest && (!dest->len || dest->cap < 0 || (!dest->p && dest->cap > 0))) return -EINVAL;
+    const size_t ncity = (size_t)nblocks * L;
+    if (!finite_cities(paths, ncity)) return -EINVAL;
+    if (nblocks == 1) {  // one rank, one block: no fold, no tree (nothing to launch or load)
+        *final_cost = costs[0];
+        if (dest) {
+            *dest->len = L;
+            if (dest->cap > 0) std::memcpy(dest->p, paths, (size_t)std::min(L, dest->cap) * sizeof(tspgpu_city));
+            if (dest->cap < L) return -ENOSPC;
+        }
+        return 0;
+    }
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return -ENODEV;
+    const double dmax = bbox_diagonal(paths, ncity);
+    DVec blocks;
+    int rc = blocks.reserve(ncity, ctx->stream);
+    if (!rc) rc = herr(xcopy_async(blocks.p, paths, ncity * sizeof(tspgpu_city), hipMemcpyHostToDevice, ctx->stream));
+    if (!rc) rc = herr(hipStreamSynchronize(ctx->stream));
+    blocks.len = ncity;
+    std::string text;
+    if (!rc)
+        rc = reduce_core(ctx, blocks.p, L, costs, nblocks, nprocs, dmax, host_fold_ok(paths, L, nblocks), final_cost,
+                         text, dest);
+    blocks.release();
+    if (rc) return rc;
+    put_log(text, log, logcap);
+    return dest && *dest->len > dest->cap ? -ENOSPC : 0;
+}
+
+// a hipEvent_t that lives for one call
+struct EventPair {
+    hipEvent_t a = nullptr;
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+    }
+};
 
 }  // namespace
 
@@ -1055,112 +1237,152 @@ int tspgpu_merge(tspgpu_ctx *ctx, const tspgpu_city *p1, int L1, double c1, cons
 int tspgpu_reduce(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
                   double *final_cost, char *log, int logcap)
 {
-    if (log && logcap > 0) log[0] = 0;
-    if (!ctx || !paths || !costs || !final_cost) return -EINVAL;
-    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || L < 2) return -EINVAL;
-    const size_t ncity = (size_t)nblocks * L;
-    if (!finite_cities(paths, ncity)) return -EINVAL;
-    if (nblocks == 1) {  // one rank, one block: no fold, no tree (nothing to launch or load)
-        *final_cost = costs[0];
-        return 0;
+    return reduce_host(ctx, paths, L, costs, nblocks, nprocs, final_cost, nullptr, log, logcap);
+}
+
+int tspgpu_reduce_path(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
+                       double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log, int logcap)
+{
+    if (!path_len) {
+        if (log && logcap > 0) log[0] = 0;
+        return -EINVAL;
     }
+    const PathDest dest{path_out, false, path_cap, path_len};
+    return reduce_host(ctx, paths, L, costs, nblocks, nprocs, final_cost, &dest, log, logcap);
+}
+
+int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *d_tour, const double *d_cost,
+                         const int32_t *d_status, int n, int nblocks, int nprocs, double *final_cost,
+                         tspgpu_city *d_path_out, int path_cap, int *path_len, char *log, int logcap, void *hip_stream)
+{
+    using tspgpu::PathFacts;
+    if (log && logcap > 0) log[0] = 0;
+    if (!ctx || !d_cities || !d_tour || !d_cost || !final_cost || !path_len) return -EINVAL;
+    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || n < 2 || n > TSPGPU_MAX_CITIES) return -EINVAL;
+    if (path_cap < 0 || (!d_path_out && path_cap > 0)) return -EINVAL;
+    const int L = tspgpu_tour_length(n);
+    const size_t ncity = (size_t)nblocks * L;
+    if (ncity > (size_t)INT_MAX) return -EINVAL;  // (path lengths are ints throughout K3)
     std::lock_guard<std::mutex> g(ctx->mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return -ENODEV;
-    Merger m;
-    int rc = m.init(ctx, bbox_diagonal(paths, ncity));
-    if (rc) return rc;
+    hipStream_t st = ctx->stream, caller = (hipStream_t)hip_stream;
+    EventPair order;
+    hipError_t e = hipSuccess;
+    if (caller != st) {
+        // K1's outputs were produced on the caller's stream
+        e = hipEventCreateWithFlags(&order.a, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(order.a, caller);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, order.a, 0);
+        if (e != hipSuccess) return herr(e);
+    }
+    // per call: the gathered paths, the facts, the id bitmap
     DVec blocks;
-    rc = blocks.reserve(ncity, m.st);
-    if (!rc) rc = herr(xcopy_async(blocks.p, paths, ncity * sizeof(tspgpu_city), hipMemcpyHostToDevice, m.st));
-    if (!rc) rc = herr(hipStreamSynchronize(m.st));
-    blocks.len = ncity;
-    // distributeBlocks' counts (tsp.cpp:167-192): rank r gets #{b in [1,B] : b mod P == r}
-    std::vector<int> cnt(nprocs, 0);
-    for (int b = nblocks; b > 0; --b) cnt[b % nprocs]++;
-    // one-kernel fold merges need block tours that close on their first city
-    // and ids unique across blocks (the reference's generator numbers cities
-    // globally); anything else takes the general path
-    bool fold_ok = L >= 3;
-    if (fold_ok) {
-        std::vector<int> ids;
-        ids.reserve((size_t)nblocks * (L - 1));
-        for (int b = 0; b < nblocks && fold_ok; ++b) {
-            const tspgpu_city *pb = paths + (size_t)b * L;
-            if (pb[0].id != pb[L - 1].id) fold_ok = false;
-            for (int k = 0; k < L - 1; ++k) ids.push_back(pb[k].id);
-        }
-        std::sort(ids.begin(), ids.end());
-        if (fold_ok && std::adjacent_find(ids.begin(), ids.end()) != ids.end()) fold_ok = false;
-    }
-    // Every buffer a queued merge may touch is sized up front (a merged path
-    // never exceeds all cities; a received list never exceeds all cities), so
-    // nothing is reallocated while merges are in flight.
-    std::vector<DVec> rank(nprocs), received(nprocs);
-    DVec tmp;
-    std::vector<double> rcost(nprocs, 0.0);
-    if (!rc) rc = tmp.reserve(ncity, m.st);
-    int next = 0;
-    if (!rc && fold_ok && L <= kFoldL2 && tspgpu::tuned_or("K3_PERSIST", 1) != 0) {
-        // (tuning knob K3_PERSIST = 0: the per-merge launches instead; tests compare both)
-        // every rank's fold in one persistent launch (fold_persist_kernel)
-        rc = persist_folds(m, blocks.p, L, costs, cnt, rank, tmp, rcost);
-        next = nblocks;
-    }
-    for (int r = 0; r < nprocs && !rc && next < nblocks; ++r) {
-        rc = rank[r].reserve(ncity, m.st);
-        if (rc) break;
-        rc = herr(xcopy_async(rank[r].p, blocks.p + (size_t)next * L, L * sizeof(tspgpu_city),
-                                 hipMemcpyDeviceToDevice, m.st));
-        rank[r].len = L;
-        rcost[r] = costs[next];
-        ++next;
-        // each logical rank folds its contiguous block range left (tsp.cpp:348-352)
-        for (int j = 1; j < cnt[r] && !rc; ++j, ++next)
-            rc = m.merge(rank[r], tmp, &rcost[r], blocks.p + (size_t)next * L, L, &costs[next], fold_ok);
-    }
-    // MPI_ManualReduce (tsp.cpp:52-134): the receiver appends every received
-    // path to one function-local list and merges with the WHOLE list
-    // (tsp.cpp:67,93-98,115-120)
-    std::string text;
-    auto receive = [&](int to, int from) -> int {
-        // the copy below reads rank[from]'s final path: every queued merge
-        // (and any stall) must be resolved first
-        int r2 = m.sync();
-        if (r2) return r2;
-        DVec &acc = received[to];
-        const size_t add = rank[from].len;
-        r2 = acc.reserve(std::max(acc.len + add, ncity), m.st);
-        if (r2) return r2;
-        r2 = herr(xcopy_async(acc.p + acc.len, rank[from].p, add * sizeof(tspgpu_city), hipMemcpyDeviceToDevice,
-                                 m.st));
-        if (r2) return r2;
-        acc.len += add;
-        return m.merge(rank[to], tmp, &rcost[to], acc.p, (int)acc.len, &rcost[from]);
+    PathFacts *d_facts = nullptr;
+    uint32_t *d_bitmap = nullptr;
+    const size_t bitmap_bytes = (size_t)tspgpu::path_bitmap_bytes(nblocks, L);  // (whole words)
+    auto release = [&] {
+        blocks.release();
+        if (d_facts) (void)hipFree(d_facts);
+        if (d_bitmap) (void)hipFree(d_bitmap);
     };
-    const int lastpower = 1 << (int)std::log2((double)nprocs);
-    for (int i = 0; i < nprocs - lastpower && !rc; ++i) {
-        char line[128];
-        std::snprintf(line, sizeof line, "process %i is about to receive %i cities from process %i\n", i,
-                      (int)rank[i + lastpower].len, i + lastpower);  // tsp.cpp:88
-        text += line;
-        rc = receive(i, i + lastpower);
+    int rc = blocks.reserve(ncity, st);
+    if (!rc) rc = herr(hipMalloc((void **)&d_facts, sizeof(PathFacts)));
+    if (!rc && L >= 3) rc = herr(hipMalloc((void **)&d_bitmap, bitmap_bytes));
+    // (the timing events are the context's, created on the first call)
+    if (!rc && !ctx->ev_k3_gather[0]) rc = herr(hipEventCreate(&ctx->ev_k3_gather[0]));
+    if (!rc && !ctx->ev_k3_gather[1]) rc = herr(hipEventCreate(&ctx->ev_k3_gather[1]));
+    PathFacts facts = tspgpu::path_facts_init();
+    std::vector<double> costs((size_t)nblocks);
+    const int grid_cap = ctx->cu_count * 8;
+    if (!rc) rc = herr(xcopy_async(d_facts, &facts, sizeof facts, hipMemcpyHostToDevice, st));
+    if (!rc && d_bitmap) rc = herr(hipMemsetAsync(d_bitmap, 0, bitmap_bytes, st));
+    if (!rc) rc = herr(hipEventRecord(ctx->ev_k3_gather[0], st));
+    if (!rc)
+        rc = herr(tspgpu::launch_paths_gather(d_cities, d_tour, d_status, n, nblocks, blocks.p, d_facts, grid_cap,
+                                              st));
+    if (!rc && d_bitmap)
+        rc = herr(tspgpu::launch_paths_unique(blocks.p, L, nblocks, d_bitmap, d_facts, grid_cap, st));
+    if (!rc) rc = herr(hipEventRecord(ctx->ev_k3_gather[1], st));
+    // (the D2H copies are complete when they return: xfer.h)
+    if (!rc) rc = herr(xcopy_async(&facts, d_facts, sizeof facts, hipMemcpyDeviceToHost, st));
+    if (!rc) rc = herr(xcopy_async(costs.data(), d_cost, costs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!rc) rc = herr(hipStreamSynchronize(st));
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        release();
+        return rc;
     }
-    for (int d = 0; d < (int)std::log2((double)lastpower) && !rc; ++d)
-        for (int k = 0; k < lastpower && !rc; k += 1 << (d + 1)) rc = receive(k, k + (1 << d));
-    if (!rc) rc = m.sync();
-    (void)hipStreamSynchronize(m.st);
-    for (auto &v : rank) v.release();
-    for (auto &v : received) v.release();
-    tmp.release();
-    blocks.release();
+    blocks.len = ncity;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, ctx->ev_k3_gather[0], ctx->ev_k3_gather[1]) == hipSuccess) ctx->k3_gather_ms = ms;
+    rc = tspgpu::path_facts_error(facts);
+    std::string text;
+    if (!rc && nblocks == 1) {  // one rank, one block: no fold, no tree
+        *final_cost = costs[0];
+        *path_len = L;
+        const size_t k = (size_t)std::min(L, path_cap);
+        if (k) rc = herr(xcopy_async(d_path_out, blocks.p, k * sizeof(tspgpu_city), hipMemcpyDeviceToDevice, st));
+        if (!rc) rc = herr(hipStreamSynchronize(st));
+    } else if (!rc) {
+        // the host's own formula over the device's exact extrema: the bits of bbox_diagonal
+        const double dmax = tspgpu::path_facts_diagonal(facts);
+        const bool fold_ok = tspgpu::path_facts_fold_ok(facts, L);
+        const PathDest dest{d_path_out, true, path_cap, path_len};
+        rc = reduce_core(ctx, blocks.p, L, costs.data(), nblocks, nprocs, dmax, fold_ok, final_cost, text, &dest);
+    }
+    release();
     if (rc) return rc;
-    *final_cost = rcost[0];
-    if (log && logcap > 0) {
-        const size_t k = std::min(text.size(), (size_t)logcap - 1);
-        std::memcpy(log, text.data(), k);
-        log[k] = 0;
-    }
+    put_log(text, log, logcap);
+    return *path_len > path_cap ? -ENOSPC : 0;
+}
+
+int tspgpu_reduce_device_last_ms(const tspgpu_ctx *ctx, double *gather_ms)
+{
+    if (!ctx) return -EINVAL;
+    // (written by tspgpu_reduce_device under the context's mutex)
+    std::lock_guard<std::mutex> g(const_cast<tspgpu_ctx *>(ctx)->mu);
+    if (gather_ms) *gather_ms = ctx->k3_gather_ms;
     return 0;
+}
+
+int tspgpu_pipeline_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, int nblocks, int nprocs,
+                           double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log,
+                           int logcap)
+{
+    if (log && logcap > 0) log[0] = 0;
+    if (!ctx || !cities || !final_cost || !path_len) return -EINVAL;
+    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || n < 2 || n > TSPGPU_MAX_CITIES) return -EINVAL;
+    if (path_cap < 0 || (!path_out && path_cap > 0)) return -EINVAL;
+    // per call: the cities, K1's outputs and the merged tour on the device.
+    // (each step takes the context's mutex itself; the buffers are this call's)
+    const size_t ib = (size_t)nblocks * n * sizeof(tspgpu_city);
+    const size_t tb = (size_t)nblocks * (n + 1) * sizeof(int32_t);
+    void *d_cities = nullptr, *d_cost = nullptr, *d_tour = nullptr, *d_status = nullptr, *d_path = nullptr;
+    int rc = tspgpu_device_alloc(ctx, ib, &d_cities);
+    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(double), &d_cost);
+    if (!rc) rc = tspgpu_device_alloc(ctx, tb, &d_tour);
+    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(int32_t), &d_status);
+    if (!rc && path_cap > 0) rc = tspgpu_device_alloc(ctx, (size_t)path_cap * sizeof(tspgpu_city), &d_path);
+    void *st = tspgpu_stream(ctx);
+    if (!rc) rc = tspgpu_memcpy_htod(ctx, d_cities, cities, ib);
+    if (!rc)
+        rc = tspgpu_solve_cities_device(ctx, (const tspgpu_city *)d_cities, n, nblocks, (double *)d_cost,
+                                        (int32_t *)d_tour, (int32_t *)d_status, st);
+    int red = 0;
+    if (!rc) {
+        red = tspgpu_reduce_device(ctx, (const tspgpu_city *)d_cities, (const int32_t *)d_tour, (const double *)d_cost,
+                                   (const int32_t *)d_status, n, nblocks, nprocs, final_cost, (tspgpu_city *)d_path,
+                                   path_cap, path_len, log, logcap, st);
+        if (red == 0 || red == -ENOSPC) {
+            const size_t k = (size_t)std::min(*path_len, path_cap);
+            if (k) rc = tspgpu_memcpy_dtoh(ctx, path_out, d_path, k * sizeof(tspgpu_city));
+        }
+    } else {
+        (void)tspgpu_stream_synchronize(ctx, st);
+    }
+    for (void *p : {d_cities, d_cost, d_tour, d_status, d_path})
+        if (p) (void)tspgpu_device_free(ctx, p);
+    return rc ? rc : red;
 }
 
 }  // extern "C"

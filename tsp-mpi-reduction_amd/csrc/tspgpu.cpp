@@ -637,6 +637,8 @@ void tspgpu_ctx_release(tspgpu_ctx *c)
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     if (c->ev_k1_done) (void)hipEventDestroy(c->ev_k1_done);
+    for (hipEvent_t ev : c->ev_k3_gather)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto ev : c->ev_split) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;

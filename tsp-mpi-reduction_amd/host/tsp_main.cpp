@@ -29,6 +29,12 @@
 // TSP_STATS=1 adds one statistics line on stderr (phase times, relaxations/s).
 // TSP_DEVICE_DIST=1 builds the distance matrices on the GPU from uploaded
 // cities (tspgpu_solve_cities_upload) instead of on the host; same output.
+// TSP_DEVICE_PIPELINE=1 runs block search and merges as one call that keeps
+// K1's results on the GPU (tspgpu_pipeline_cities); same output.  A single
+// process with TSP_GPUS <= 1 and no TSP_HOST_MERGE only: otherwise it is
+// ignored (TSP_STATS says so).
+// TSP_TOUR_OUT=FILE writes the merged tour's city ids, one per line (rank 0's
+// final path, closing city included), in either mode; not with TSP_HOST_MERGE.
 //
 // Deviations (documented in DESIGN.md), all where the reference is undefined:
 // n < 2, numBlocks < 1 or numBlocks < P exit 2 with a message on stderr
@@ -270,6 +276,27 @@ int read_rank_files(const std::string &dir, uint64_t key, int P, int n, int B, i
     return 0;
 }
 
+// Capacity for rank 0's final path: all cities plus the closing one at P = 1;
+// the reference's stale receive lists repeat cities for P > 1 (the length
+// grows by about 1.31 per tree round), so room for (2 + log2 P) times the
+// cities, and the caller asks again with the reported length if that is short.
+size_t tour_capacity(int B, int L, int P)
+{
+    int rounds = 0;
+    while ((1 << (rounds + 1)) <= P) ++rounds;
+    return (size_t)B * L * (P > 1 ? 2 + rounds : 1) + 1;
+}
+
+int write_tour(const char *file, const tspgpu_city *path, int len)
+{
+    FILE *f = std::fopen(file, "w");
+    if (!f) return -errno;
+    bool ok = true;
+    for (int i = 0; i < len && ok; ++i) ok = std::fprintf(f, "%d\n", path[i].id) > 0;
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? 0 : -EIO;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -344,8 +371,6 @@ int main(int argc, char **argv)
     std::vector<tspgpu_city> cities((size_t)B * n);
     tsphost_generate(n, B, X, Y, cities.data());
 
-    std::vector<double> cost(B, 0.0);
-    std::vector<int32_t> tour((size_t)B * (n + 1), -1);
     int rc;
     timespec ts_solve0, ts_solve1, ts_merge1;
     tspgpu_ctx *kept = nullptr;  // the block search's context on TSP_GPU, reused by the merges
@@ -356,65 +381,124 @@ int main(int argc, char **argv)
     timespec ts_rt;
     (void)tspgpu_device_count();
     clock_gettime(CLOCK_MONOTONIC_RAW, &ts_rt);
-    if (multi) {
-        // rank 0's own share here, the other ranks' shares from their files
-        std::vector<int> cnt(P), off(P, 0);
-        tsphost_distribution_counts(B, P, cnt.data());
-        for (int r = 1; r < P; ++r) off[r] = off[r - 1] + cnt[r - 1];
-        const uint64_t key = job_key(n, B, X, Y);
-        int failed = 0;
-        rc = solve_range(cities, n, 0, cnt[0], env_int("TSP_GPUS", 1), env_int("TSP_GPU", 0), cost.data(), tour.data(),
-                         &kept, &dist_ms);
-        if (!rc) rc = read_rank_files(gather_dir(key), key, P, n, B, X, Y, cnt, off, cost.data(), tour.data(), &failed);
-        if (rc && failed) {
-            std::fflush(stdout);
-            std::fprintf(stderr, "tsp: rank %d failed: %s (%d)\n", failed, tspgpu_strerror(rc), rc);
-            return 3;
-        }
-    } else {
-        rc = solve_range(cities, n, 0, B, env_int("TSP_GPUS", 1), env_int("TSP_GPU", 0), cost.data(), tour.data(),
-                         &kept, &dist_ms);
-    }
-    if (rc) {
-        std::fflush(stdout);
-        std::fprintf(stderr, "tsp: GPU block search failed: %s (%d)\n", tspgpu_strerror(rc), rc);
-        return 3;
-    }
-
-    clock_gettime(CLOCK_MONOTONIC_RAW, &ts_solve1);
-    // convPathToCityPath (assignment2.h:76-84) for every block
+    const char *tour_file = std::getenv("TSP_TOUR_OUT");
+    if (tour_file && !*tour_file) tour_file = nullptr;
+    const bool host_merge = env_int("TSP_HOST_MERGE", 0) != 0;
+    const bool pipeline_asked = env_int("TSP_DEVICE_PIPELINE", 0) != 0;
+    const bool pipeline = pipeline_asked && !multi && env_int("TSP_GPUS", 1) <= 1 && !host_merge;
     const int L = tspgpu_tour_length(n);
-    std::vector<tspgpu_city> paths((size_t)B * L);
-    for (int b = 0; b < B; ++b)
-        for (int i = 0; i < L; ++i) paths[(size_t)b * L + i] = cities[(size_t)b * n + tour[(size_t)b * (n + 1) + i]];
-
-    // the fold + reduction tree: K3 on the GPU (default), or the host replay
-    // (TSP_HOST_MERGE=1); both reproduce the reference's mergeBlocks exactly
+    std::vector<tspgpu_city> merged;  // rank 0's final path (TSP_TOUR_OUT, the device pipeline)
+    int merged_len = -1;
     double final_cost = 0.0;
     std::vector<char> log(1 << 20);
     int red = 0;
-    if (env_int("TSP_HOST_MERGE", 0)) {
-        if (kept) tspgpu_ctx_destroy(kept);
-        kept = nullptr;
-        red = tsphost_reduce(paths.data(), L, cost.data(), B, P, &final_cost, log.data(), (int)log.size()) ? -EDEADLK
-                                                                                                          : 0;
-    } else {
+    if (pipeline) {
+        // block search and merges in one call, K1's results stay on the GPU
         tspgpu_opts o;
         std::memset(&o, 0, sizeof o);
-        o.device = env_int("TSP_GPU", 0);
-        red = kept ? 0 : tspgpu_ctx_create(&o, &kept);
-        if (!red) red = tspgpu_reduce(kept, paths.data(), L, cost.data(), B, P, &final_cost, log.data(), (int)log.size());
+        o.device = env_int("TSP_GPU", 0) % visible_devices();
+        o.strict = 1;
+        rc = tspgpu_ctx_create(&o, &kept);
+        if (rc) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "tsp: GPU block search failed: %s (%d)\n", tspgpu_strerror(rc), rc);
+            return 3;
+        }
+        merged.resize(tour_file ? tour_capacity(B, L, P) : 0);
+        red = tspgpu_pipeline_cities(kept, cities.data(), n, B, P, &final_cost, merged.data(), (int)merged.size(),
+                                     &merged_len, log.data(), (int)log.size());
+        if (red == -ENOSPC && tour_file) {
+            merged.resize((size_t)merged_len);
+            red = tspgpu_pipeline_cities(kept, cities.data(), n, B, P, &final_cost, merged.data(),
+                                         (int)merged.size(), &merged_len, log.data(), (int)log.size());
+        } else if (red == -ENOSPC) {
+            red = 0;  // (the tour was not asked for)
+        }
+        double build_ms = 0.0, pow_ms = 0.0;
+        if (!red && !tspgpu_cities_last_phase_ms(kept, &build_ms, &pow_ms)) dist_ms = build_ms + pow_ms;
+        clock_gettime(CLOCK_MONOTONIC_RAW, &ts_solve1);
+    } else {
+        std::vector<double> cost(B, 0.0);
+        std::vector<int32_t> tour((size_t)B * (n + 1), -1);
+        if (multi) {
+            // rank 0's own share here, the other ranks' shares from their files
+            std::vector<int> cnt(P), off(P, 0);
+            tsphost_distribution_counts(B, P, cnt.data());
+            for (int r = 1; r < P; ++r) off[r] = off[r - 1] + cnt[r - 1];
+            const uint64_t key = job_key(n, B, X, Y);
+            int failed = 0;
+            rc = solve_range(cities, n, 0, cnt[0], env_int("TSP_GPUS", 1), env_int("TSP_GPU", 0), cost.data(),
+                             tour.data(), &kept, &dist_ms);
+            if (!rc)
+                rc = read_rank_files(gather_dir(key), key, P, n, B, X, Y, cnt, off, cost.data(), tour.data(),
+                                     &failed);
+            if (rc && failed) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "tsp: rank %d failed: %s (%d)\n", failed, tspgpu_strerror(rc), rc);
+                return 3;
+            }
+        } else {
+            rc = solve_range(cities, n, 0, B, env_int("TSP_GPUS", 1), env_int("TSP_GPU", 0), cost.data(),
+                             tour.data(), &kept, &dist_ms);
+        }
+        if (rc) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "tsp: GPU block search failed: %s (%d)\n", tspgpu_strerror(rc), rc);
+            return 3;
+        }
+
+        clock_gettime(CLOCK_MONOTONIC_RAW, &ts_solve1);
+        // convPathToCityPath (assignment2.h:76-84) for every block
+        std::vector<tspgpu_city> paths((size_t)B * L);
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < L; ++i)
+                paths[(size_t)b * L + i] = cities[(size_t)b * n + tour[(size_t)b * (n + 1) + i]];
+
+        // the fold + reduction tree: K3 on the GPU (default), or the host replay
+        // (TSP_HOST_MERGE=1); both reproduce the reference's mergeBlocks exactly
+        if (host_merge) {
+            if (kept) tspgpu_ctx_destroy(kept);
+            kept = nullptr;
+            red = tsphost_reduce(paths.data(), L, cost.data(), B, P, &final_cost, log.data(), (int)log.size())
+                      ? -EDEADLK
+                      : 0;
+        } else {
+            tspgpu_opts o;
+            std::memset(&o, 0, sizeof o);
+            o.device = env_int("TSP_GPU", 0);
+            red = kept ? 0 : tspgpu_ctx_create(&o, &kept);
+            if (!red && !tour_file) {
+                red = tspgpu_reduce(kept, paths.data(), L, cost.data(), B, P, &final_cost, log.data(),
+                                    (int)log.size());
+            } else if (!red) {
+                merged.resize(tour_capacity(B, L, P));
+                for (int pass = 0; pass < 2; ++pass) {
+                    red = tspgpu_reduce_path(kept, paths.data(), L, cost.data(), B, P, &final_cost, merged.data(),
+                                             (int)merged.size(), &merged_len, log.data(), (int)log.size());
+                    if (red != -ENOSPC) break;
+                    merged.resize((size_t)merged_len);
+                }
+            }
+        }
     }
     if (red) {
         std::fflush(stdout);
         if (red == -EDEADLK)
             std::fprintf(stderr, "tsp: the reference's merge would not terminate for these blocks\n");
+        else if (pipeline)
+            std::fprintf(stderr, "tsp: GPU block search or merge failed: %s (%d)\n", tspgpu_strerror(red), red);
         else
             std::fprintf(stderr, "tsp: GPU merge failed: %s (%d)\n", tspgpu_strerror(red), red);
-        return 2;
+        return pipeline && red != -EDEADLK ? 3 : 2;
     }
     std::fputs(log.data(), stdout);
     clock_gettime(CLOCK_MONOTONIC_RAW, &ts_merge1);
+    if (tour_file && merged_len >= 0) {
+        const int wrc = write_tour(tour_file, merged.data(), merged_len);
+        if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));
+    } else if (tour_file) {
+        std::fprintf(stderr, "tsp: TSP_TOUR_OUT is not written with TSP_HOST_MERGE\n");
+    }
 
     clock_gettime(CLOCK_MONOTONIC_RAW, &end);
     const uint64_t ms = (uint64_t)((1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6);
@@ -436,12 +520,16 @@ int main(int argc, char **argv)
         std::fprintf(stderr,
                      "tsp stats: n %d blocks %d ranks %d | setup %.3f ms, block search %.3f ms (HIP runtime start-up "
                      "%.3f ms of it, distances %.3f ms of it on the %s; %s), merge %.3f ms, total %.3f ms | %.4g DP "
-                     "relaxations/s\n",
+                     "relaxations/s%s\n",
                      n, B, P, 1e3 * sec(start, ts_solve0), 1e3 * solve_s, 1e3 * sec(ts_solve0, ts_rt), dist_ms,
-                     env_int("TSP_DEVICE_DIST", 0) ? "device" : "host",
+                     pipeline || env_int("TSP_DEVICE_DIST", 0) ? "device" : "host",
                      multi ? "rank 0's share + the rank files" : "all blocks, one process",
                      1e3 * sec(ts_solve1, ts_merge1), 1e3 * sec(start, end),
-                     solve_s > 0 && relax > 0 ? relax / solve_s : 0.0);
+                     solve_s > 0 && relax > 0 ? relax / solve_s : 0.0,
+                     pipeline ? " | device pipeline: block search and merge are one call, timed as the block search"
+                              : (pipeline_asked ? " | TSP_DEVICE_PIPELINE ignored (one process, TSP_GPUS <= 1, no "
+                                                  "TSP_HOST_MERGE)"
+                                                : ""));
     }
     return 0;
 }

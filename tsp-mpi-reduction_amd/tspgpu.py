@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = (
     "tspgpu_select_tour", "tspgpu_tie_tour", "tspgpu_tie_tour_gpu", "tspgpu_tie_tour_records", "tspgpu_tie_key",
     # K3
     "tspgpu_merge", "tspgpu_reduce",
+    # K3 with the merged tour, and from K1's device outputs (no visit to the host in between)
+    "tspgpu_reduce_path", "tspgpu_reduce_device", "tspgpu_reduce_device_last_ms", "tspgpu_pipeline_cities",
     # K1-wide
     "tspgpu_solve_instance", "tspgpu_solve_instance_i32", "tspgpu_wide_last_dtype",
     # K1 on integer distances
@@ -202,6 +204,14 @@ def lib():
         L.tspgpu_merge.argtypes = [vp, cp, ctypes.c_int, ctypes.c_double, cp, ctypes.c_int, ctypes.c_double, cp, dp]
         L.tspgpu_reduce.argtypes = [vp, cp, ctypes.c_int, dp, ctypes.c_int, ctypes.c_int, dp, ctypes.c_char_p,
                                     ctypes.c_int]
+        intp = ctypes.POINTER(ctypes.c_int)
+        L.tspgpu_reduce_path.argtypes = [vp, cp, ctypes.c_int, dp, ctypes.c_int, ctypes.c_int, dp, cp, ctypes.c_int,
+                                         intp, ctypes.c_char_p, ctypes.c_int]
+        L.tspgpu_reduce_device.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, vp,
+                                           ctypes.c_int, intp, ctypes.c_char_p, ctypes.c_int, vp]
+        L.tspgpu_reduce_device_last_ms.argtypes = [vp, dp]
+        L.tspgpu_pipeline_cities.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, cp, ctypes.c_int,
+                                             intp, ctypes.c_char_p, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -592,6 +602,98 @@ class Context:
         if rc:
             raise TspGpuError(rc, "tspgpu_reduce")
         return final.value, log.value.decode()
+
+    @staticmethod
+    def _tour_capacity(B: int, L: int, nprocs: int) -> int:
+        """Room for rank 0's final path: every city and the closing one at one
+        rank; the reference's stale receive lists repeat cities for more (the
+        length grows by about 1.31 per tree round), so (2 + log2 P) times the
+        cities, as bin/tsp sizes it."""
+        return B * L * (2 + (nprocs.bit_length() - 1) if nprocs > 1 else 1) + 1
+
+    def reduce_path(self, paths, costs, nprocs: int, path_cap: int | None = None):
+        """K3 reduction with the merged tour (tspgpu_reduce_path): paths (B lists
+        of L cities), costs (B,) -> (final cost, log text, rank 0's final path
+        as a list of (id, x, y)).  path_cap None: room for (2 + log2 nprocs)
+        times the cities, so one reduction gives the tour; only if that is
+        ever short is the reduction run a second time with the reported
+        length.  A given path_cap below the length raises -ENOSPC, with the
+        full length in the error's path_len and the first path_cap cities in
+        its path (path_cap 0 is the length query: it still runs the whole
+        reduction)."""
+        B, L = len(paths), len(paths[0])
+        flat, _, _ = cities_array(paths)
+        c = np.ascontiguousarray(costs, dtype=np.float64)
+
+        def call(out, cap):
+            final, plen = ctypes.c_double(), ctypes.c_int(-1)
+            log = ctypes.create_string_buffer(1 << 20)
+            rc = lib().tspgpu_reduce_path(self.handle, flat, L, _dp(c), B, nprocs, ctypes.byref(final), out, cap,
+                                          ctypes.byref(plen), log, len(log))
+            return rc, final.value, log.value.decode(), plen.value
+
+        return self._path_result("tspgpu_reduce_path", call, path_cap, self._tour_capacity(B, L, nprocs))
+
+    def _path_result(self, what, call, path_cap, generous):
+        retry = path_cap is None
+        if retry:
+            path_cap = generous
+        while True:
+            out = (City * max(1, path_cap))()
+            rc, final, log, plen = call(out if path_cap > 0 else None, path_cap)
+            if rc == -errno.ENOSPC and retry and plen > path_cap:
+                path_cap, retry = plen, False  # (the whole call again, once)
+                continue
+            path = [(out[i].id, out[i].x, out[i].y) for i in range(min(plen, path_cap) if plen >= 0 else 0)]
+            if rc:
+                err = TspGpuError(rc, what)
+                err.path_len, err.path, err.cost, err.log = plen, path, final, log
+                raise err
+            return final, log, path
+
+    def reduce_device(self, d_cities_ptr: int, d_tour_ptr: int, d_cost_ptr: int, d_status_ptr: int, n: int, B: int,
+                      nprocs: int, d_path_ptr: int = 0, path_cap: int = 0, stream_ptr: int = 0):
+        """tspgpu_reduce_device: K1's device outputs (cities B*n, tour rows of
+        n+1, costs, statuses or 0) reduced without a visit to the host; the
+        merged tour goes to d_path_ptr (device, path_cap cities; 0: not wanted).
+        -> (final cost, log text, full path length).  A path_cap below the
+        length raises -ENOSPC with cost, log and path_len on the error."""
+        final, plen = ctypes.c_double(), ctypes.c_int(-1)
+        log = ctypes.create_string_buffer(1 << 20)
+        rc = lib().tspgpu_reduce_device(self.handle, d_cities_ptr, d_tour_ptr, d_cost_ptr, d_status_ptr or None, n, B,
+                                        nprocs, ctypes.byref(final), d_path_ptr or None, path_cap,
+                                        ctypes.byref(plen), log, len(log), stream_ptr or None)
+        if rc:
+            err = TspGpuError(rc, "tspgpu_reduce_device")
+            err.path_len, err.cost, err.log = plen.value, final.value, log.value.decode()
+            raise err
+        return final.value, log.value.decode(), plen.value
+
+    def reduce_device_last_ms(self) -> float:
+        """Device time (HIP events) of the last reduce_device's gather, summary and uniqueness kernels."""
+        ms = ctypes.c_double()
+        self._check(lib().tspgpu_reduce_device_last_ms(self.handle, ctypes.byref(ms)), "tspgpu_reduce_device_last_ms")
+        return ms.value
+
+    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None):
+        """tspgpu_pipeline_cities: blocks (lists of (id, x, y), or a (ctypes City
+        array, n, B) triple) -> (final cost, log text, merged tour as a list of
+        (id, x, y)): block search and merges on the device, only the costs
+        visit the host in between.  path_cap None: room for (2 + log2 nprocs)
+        times the cities, so one run gives the tour; only if that is ever
+        short does the whole pipeline run a second time with the reported
+        length."""
+        arr, n, B = blocks if isinstance(blocks, tuple) else cities_array(blocks)
+
+        def call(out, cap):
+            final, plen = ctypes.c_double(), ctypes.c_int(-1)
+            log = ctypes.create_string_buffer(1 << 20)
+            rc = lib().tspgpu_pipeline_cities(self.handle, arr, n, B, nprocs, ctypes.byref(final), out, cap,
+                                              ctypes.byref(plen), log, len(log))
+            return rc, final.value, log.value.decode(), plen.value
+
+        return self._path_result("tspgpu_pipeline_cities", call, path_cap,
+                                 self._tour_capacity(B, tour_length(n), nprocs))
 
     def device_info(self):
         cu = ctypes.c_int()
