@@ -219,6 +219,41 @@ int tspgpu_solve_cities_upload(tspgpu_ctx *ctx, const tspgpu_city *cities, int n
 int tspgpu_cities_last_fixups(const tspgpu_ctx *ctx, uint64_t *squares, uint64_t *flagged, int *build_passes);
 int tspgpu_cities_last_phase_ms(const tspgpu_ctx *ctx, double *build_ms, double *pow_ms);
 
+/* ---------------------------------------------------------------------------
+ * Ragged blocks from cities: blocks of DIFFERENT city counts,
+ * PACKED.  Block b has n[b] cities at cities + (n[0] + ... + n[b-1]), in
+ * caller order; n[] is a HOST array, read before the call returns.  The
+ * packed layout is undefined unless every n[b] is in range, so an n[b]
+ * outside [2, TSPGPU_MAX_CITIES] ([1, TSPGPU_MAX_CITIES] for the distance
+ * form) is a call-level error: -EINVAL, nothing launched, no output written,
+ * like a NULL context, a NULL pointer with nblocks > 0, nblocks < 0 or
+ * tour_stride < (largest n[b]) + 1.  nblocks == 0 returns 0.  On a strict
+ * context an n[b] of 17..20 is a per-block -EINVAL status instead (its cities
+ * are skipped, the layout stays defined).
+ * ------------------------------------------------------------------------- */
+/* tspgpu_distance_matrix_device for packed ragged blocks: computeDistanceMatrix
+ * of every block into d_dist, the matrices packed too (block b at element
+ * n[0]^2 + ... + n[b-1]^2), each with the bits of tspgpu_distance_matrix on
+ * that block alone.  Same protocol, fix-up list (a quarter of the sum of
+ * n[b]*(n[b]-1) entries, or the knob DIST_FIX_CAP), overflow retry and
+ * synchronisation as the uniform form; tspgpu_cities_last_fixups and
+ * tspgpu_cities_last_phase_ms report this build too. */
+int tspgpu_distance_matrix_ragged_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *n, int nblocks,
+                                         double *d_dist, void *hip_stream);
+/* The matrices into a context buffer, then tspgpu_solve_ragged_device with
+ * the packed offsets: the ragged contract above applies unchanged (d_status,
+ * NaN cost, a tour row of -1; rows of tour_stride entries, padded with -1).
+ * A non-finite coordinate fails its own block only.  Synchronises the stream
+ * as tspgpu_distance_matrix_device does; the solve is left running. */
+int tspgpu_solve_cities_ragged_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *n, int nblocks,
+                                      double *d_cost, int32_t *d_tour, int tour_stride, int32_t *d_status,
+                                      void *hip_stream);
+/* Host-pointer form, synchronous: uploads the cities, runs the device form on
+ * the context's stream, copies cost, tour and status back.  Returns 0 however
+ * many blocks are bad, like tspgpu_solve_ragged. */
+int tspgpu_solve_cities_ragged(tspgpu_ctx *ctx, const tspgpu_city *cities, const int32_t *n, int nblocks,
+                               double *cost_out, int32_t *tour_out, int tour_stride, int32_t *status_out);
+
 /* Context-free convenience form (uses a per-thread default context on the
  * current device, created on first use). */
 int tspgpu_solve(const double *dist, int n, int nblocks, double *cost_out, int32_t *tour_out,
@@ -570,6 +605,34 @@ int tspgpu_reduce_device_last_ms(const tspgpu_ctx *ctx, double *gather_ms);
 int tspgpu_pipeline_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, int nblocks, int nprocs,
                            double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log,
                            int logcap);
+/* The three forms above for blocks of DIFFERENT sizes (the
+ * reference's mergeBlocks takes two paths of any length).  Call-level errors
+ * as above, and -EINVAL for nblocks < 1, a NULL n / len, or any n[b] outside
+ * [2, TSPGPU_MAX_CITIES] (len[b] < 2): nothing is launched or written. */
+/* tspgpu_reduce_device for the outputs of tspgpu_solve_cities_ragged_device:
+ * packed cities (n[] a HOST array), tour rows of tour_stride >= (largest
+ * n[b]) + 1 entries; block b's path is tspgpu_tour_length(n[b]) cities.
+ * Status, tour entry (outside [0, n[b])), non-finite, -EDEADLK and -ENOSPC
+ * behave as there; the sum of the path lengths must be <= INT_MAX.  Ids
+ * spread wider than 8 * (that sum) take the general per-merge path, as does
+ * any batch with a 2-city block (an open path). */
+int tspgpu_reduce_ragged_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *n, const int32_t *d_tour,
+                                int tour_stride, const double *d_cost, const int32_t *d_status, int nblocks,
+                                int nprocs, double *final_cost, tspgpu_city *d_path_out, int path_cap, int *path_len,
+                                char *log, int logcap, void *hip_stream);
+/* tspgpu_reduce_path for paths of different lengths, for block tours from
+ * anywhere: paths is the concatenation, path b has len[b] >= 2 cities (host
+ * arrays).  tspgpu_reduce_path's contract; paths longer than 33 cities take
+ * the per-merge kernels instead of the one-kernel fold (same answer). */
+int tspgpu_reduce_ragged(tspgpu_ctx *ctx, const tspgpu_city *paths, const int32_t *len, const double *costs,
+                         int nblocks, int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap,
+                         int *path_len, char *log, int logcap);
+/* tspgpu_pipeline_cities for packed ragged blocks: upload,
+ * tspgpu_solve_cities_ragged_device, tspgpu_reduce_ragged_device, one copy of
+ * the tour back.  Return codes are tspgpu_pipeline_cities'. */
+int tspgpu_pipeline_cities_ragged(tspgpu_ctx *ctx, const tspgpu_city *cities, const int32_t *n, int nblocks,
+                                  int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len,
+                                  char *log, int logcap);
 
 /* ---------------------------------------------------------------------------
  * Tuning and test knobs.  The defaults are the measured best; a knob changes

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_desc.h"
 #include "tspgpu.h"
 
 namespace tspgpu {
@@ -28,5 +29,15 @@ hipError_t launch_cities_build(const tspgpu_city *cities, int n, int nblocks, do
 hipError_t launch_cities_patch(double *dist, const int64_t *fix_slot, const double *fix_val,
                                unsigned long long count, hipStream_t stream);
 hipError_t launch_cities_finish(int n, int nblocks, double *dist, hipStream_t stream);
+
+// The ragged forms: block b's n, cities and matrix are
+// desc[b]'s (device table; an entry with n = 0 is skipped); fix_slot indexes
+// the whole packed dist array as above.  Every desc[b].n must be in
+// [0, kCitiesMaxN] (the caller checks: the kernels stage a block in LDS rows
+// of kCitiesMaxN).
+hipError_t launch_cities_build_ragged(const tspgpu_city *cities, const BlockDesc *desc, int nblocks, double *dist,
+                                      int64_t *fix_slot, double *fix_dx, unsigned long long fix_cap,
+                                      unsigned long long *fix_count, hipStream_t stream);
+hipError_t launch_cities_finish_ragged(const BlockDesc *desc, int nblocks, double *dist, hipStream_t stream);
 
 }  // namespace tspgpu

@@ -7,6 +7,13 @@
 // 256-thread workgroup; a lane owns the pairs lane, lane + 64, lane + 128 of
 // the block's n(n-1)/2 (at most 190).  Built without the K1 kernels'
 // -fno-honor-nans: a NaN coordinate must stay a NaN distance.
+//
+// The ragged forms are the same kernels with one difference:
+// a wave takes its block's (city offset, matrix offset, n) from the descriptor
+// table (block_desc.h) where the uniform form computes b*n, b*n*n and reads n
+// from the arguments.  n is uniform within a wave, so every lane still makes
+// the same kCtPasses trips and reaches every ballot; the four waves of a
+// workgroup may hold blocks of four different sizes.
 #include "cities.h"
 
 #include "dist_exact.h"
@@ -45,8 +52,30 @@ __device__ __forceinline__ int lanes_below(uint64_t ballot)
 // every flagged square's (slot, operand) appended to the fix-up list with one
 // atomic add per wave.  The diagonal is final here: +0.0, or NaN where a
 // coordinate is not finite (x - x is NaN then, as in the reference).
+// Where block b lies: computed (uniform) or read from the table (ragged; the
+// whole wave reads one entry, n made a scalar).
+template <bool kRagged>
+__device__ __forceinline__ void block_place(const BlockDesc *__restrict__ desc, int64_t b, bool live, int &n,
+                                            int64_t &city, int64_t &base)
+{
+    if constexpr (kRagged) {
+        n = 0, city = 0, base = 0;
+        if (live) {
+            const BlockDesc e = desc[b];
+            n = e.n, city = e.city, base = e.dist;
+            if (n < 0 || n > kCitiesMaxN) n = 0;  // (the fronts refuse such a table: the LDS rows hold kCitiesMaxN)
+        }
+        n = __builtin_amdgcn_readfirstlane(n);
+    } else {
+        city = b * n;
+        base = b * n * n;
+    }
+}
+
+template <bool kRagged>
 __global__ __launch_bounds__(kCtThreads) void cities_build_kernel(const tspgpu_city *__restrict__ cities, int n,
-                                                                 int nblocks, double *__restrict__ dist,
+                                                                 const BlockDesc *__restrict__ desc, int nblocks,
+                                                                 double *__restrict__ dist,
                                                                  int64_t *__restrict__ fix_slot,
                                                                  double *__restrict__ fix_dx,
                                                                  unsigned long long fix_cap,
@@ -57,15 +86,16 @@ __global__ __launch_bounds__(kCtThreads) void cities_build_kernel(const tspgpu_c
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t b = (int64_t)blockIdx.x * kCtWaves + wave;
     const bool live = b < nblocks;
+    int64_t city, base;
+    block_place<kRagged>(desc, b, live, n, city, base);
     if (live && lane < n) {
-        const tspgpu_city c = cities[b * n + lane];
+        const tspgpu_city c = cities[city + lane];
         sx[wave][lane] = c.x;
         sy[wave][lane] = c.y;
     }
     __syncthreads();
     if (!live) return;
     const int pairs = n * (n - 1) / 2;
-    const int64_t base = b * n * n;
     double *d = dist + base;
     if (lane < n) {
         const double zx = sx[wave][lane] - sx[wave][lane], zy = sy[wave][lane] - sy[wave][lane];
@@ -137,14 +167,18 @@ __global__ __launch_bounds__(kCtThreads) void cities_patch_kernel(double *__rest
 // Finish: the two squares of a pair sit at d[i][j] and d[j][i]; both entries
 // become sqrt_rn of their sum (the lane that owns the pair is the only one
 // that touches either).
-__global__ __launch_bounds__(kCtThreads) void cities_finish_kernel(int n, int nblocks, double *__restrict__ dist)
+template <bool kRagged>
+__global__ __launch_bounds__(kCtThreads) void cities_finish_kernel(int n, const BlockDesc *__restrict__ desc,
+                                                                  int nblocks, double *__restrict__ dist)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t b = (int64_t)blockIdx.x * kCtWaves + wave;
     if (b >= nblocks) return;
+    int64_t city, base;
+    block_place<kRagged>(desc, b, true, n, city, base);
     const int pairs = n * (n - 1) / 2;
-    double *d = dist + b * n * n;
+    double *d = dist + base;
 #pragma unroll
     for (int p = 0; p < kCtPasses; ++p) {
         const int k = lane + 64 * p;
@@ -168,8 +202,21 @@ hipError_t launch_cities_build(const tspgpu_city *cities, int n, int nblocks, do
 {
     if (nblocks <= 0) return hipSuccess;
     if (n < 1 || n > kCitiesMaxN) return hipErrorInvalidValue;
-    void *args[] = {&cities, &n, &nblocks, &dist, &fix_slot, &fix_dx, &fix_cap, &fix_count};
-    return hipLaunchKernel(reinterpret_cast<const void *>(&cities_build_kernel), dim3(ct_grid(nblocks)),
+    const BlockDesc *desc = nullptr;
+    void *args[] = {&cities, &n, &desc, &nblocks, &dist, &fix_slot, &fix_dx, &fix_cap, &fix_count};
+    return hipLaunchKernel(reinterpret_cast<const void *>(&cities_build_kernel<false>), dim3(ct_grid(nblocks)),
+                           dim3(kCtThreads), args, 0, stream);
+}
+
+hipError_t launch_cities_build_ragged(const tspgpu_city *cities, const BlockDesc *desc, int nblocks, double *dist,
+                                      int64_t *fix_slot, double *fix_dx, unsigned long long fix_cap,
+                                      unsigned long long *fix_count, hipStream_t stream)
+{
+    if (nblocks <= 0) return hipSuccess;
+    if (!desc) return hipErrorInvalidValue;
+    int n = 0;
+    void *args[] = {&cities, &n, &desc, &nblocks, &dist, &fix_slot, &fix_dx, &fix_cap, &fix_count};
+    return hipLaunchKernel(reinterpret_cast<const void *>(&cities_build_kernel<true>), dim3(ct_grid(nblocks)),
                            dim3(kCtThreads), args, 0, stream);
 }
 
@@ -188,8 +235,19 @@ hipError_t launch_cities_finish(int n, int nblocks, double *dist, hipStream_t st
 {
     if (nblocks <= 0) return hipSuccess;
     if (n < 1 || n > kCitiesMaxN) return hipErrorInvalidValue;
-    void *args[] = {&n, &nblocks, &dist};
-    return hipLaunchKernel(reinterpret_cast<const void *>(&cities_finish_kernel), dim3(ct_grid(nblocks)),
+    const BlockDesc *desc = nullptr;
+    void *args[] = {&n, &desc, &nblocks, &dist};
+    return hipLaunchKernel(reinterpret_cast<const void *>(&cities_finish_kernel<false>), dim3(ct_grid(nblocks)),
+                           dim3(kCtThreads), args, 0, stream);
+}
+
+hipError_t launch_cities_finish_ragged(const BlockDesc *desc, int nblocks, double *dist, hipStream_t stream)
+{
+    if (nblocks <= 0) return hipSuccess;
+    if (!desc) return hipErrorInvalidValue;
+    int n = 0;
+    void *args[] = {&n, &desc, &nblocks, &dist};
+    return hipLaunchKernel(reinterpret_cast<const void *>(&cities_finish_kernel<true>), dim3(ct_grid(nblocks)),
                            dim3(kCtThreads), args, 0, stream);
 }
 

@@ -101,6 +101,18 @@ struct tspgpu_ctx {
     unsigned long long ct_squares = 0, ct_flagged = 0;
     int ct_passes = 0;
     double ct_build_ms = 0.0, ct_pow_ms = 0.0;
+    // Packed ragged city blocks (tspgpu_distance_matrix_ragged_device,
+    // block_desc.h): the per-block descriptor table of the build and finish
+    // kernels, uploaded from a pinned buffer under the rule of h_rg_desc
+    // (ev_bd_desc fires when the copy has read it; the next call waits for
+    // that before it writes there).  The device table is ordered like the
+    // fix-up list, behind ev_k1_done.
+    void *d_bd_desc = nullptr;
+    size_t bd_desc_bytes = 0;
+    void *h_bd_desc = nullptr;  // pinned
+    size_t h_bd_desc_bytes = 0;
+    hipEvent_t ev_bd_desc = nullptr;
+    bool bd_desc_pending = false;
     // the last tspgpu_reduce_device's gather + summary + uniqueness kernels,
     // from HIP events (tspgpu_reduce_device_last_ms)
     double k3_gather_ms = 0.0;

@@ -447,7 +447,14 @@ __device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int
     return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
 }
 
-__global__ __launch_bounds__(kFoldThreads) void fold_persist_kernel(const tspgpu_city *blocks, int L2, double eps2,
+//
+// kRagged: the blocks differ in length.  Block b then lies at
+// blocks + desc[b].path and has desc[b].L cities (block_desc.h) where the
+// uniform form has b * L2u and L2u; everything below a merge's first two lines
+// works from that merge's own (c2, L2, M) in both forms.
+template <bool kRagged>
+__global__ __launch_bounds__(kFoldThreads) void fold_persist_kernel(const tspgpu_city *blocks, int L2u,
+                                                                    const tspgpu::BlockDesc *desc, double eps2,
                                                                     const FoldJob *jobs, FoldOut *outs)
 {
     __shared__ double px[kFoldCap], py[kFoldCap];
@@ -457,11 +464,20 @@ __global__ __launch_bounds__(kFoldThreads) void fold_persist_kernel(const tspgpu
     __shared__ Top2 wtop[kFoldThreads / 64];
     const FoldJob J = jobs[blockIdx.x];
     const int t = threadIdx.x;
-    const int M = L2 - 1;
+    // block b's cities and length (the same for every thread of the workgroup)
+    auto block_at = [&](int b) -> const tspgpu_city * {
+        if constexpr (kRagged) return blocks + desc[b].path;
+        return blocks + (size_t)b * L2u;
+    };
+    auto block_len = [&](int b) -> int {
+        if constexpr (kRagged) return desc[b].L;
+        return L2u;
+    };
     int len;
     if (J.k0 == 0) {
+        const int L2 = block_len(J.first);
         len = L2;
-        const tspgpu_city *b = blocks + (size_t)J.first * L2;
+        const tspgpu_city *b = block_at(J.first);
         for (int k = t; k < L2; k += kFoldThreads) {
             const tspgpu_city c = b[k];
             px[k] = c.x, py[k] = c.y, pid[k] = c.id;
@@ -475,13 +491,14 @@ __global__ __launch_bounds__(kFoldThreads) void fold_persist_kernel(const tspgpu
     }
     int status = 0, at = J.count - 1, nc = 1;
     for (int m = J.k0; m < J.count - 1; ++m) {
-        if (len + M > kFoldCap) {
+        const int L2 = block_len(J.first + 1 + m), M = L2 - 1;
+        if (len + M > kFoldCap || L2 > kFoldL2) {  // (the host sends no block above kFoldL2 here)
             status = 2, at = m;
             break;
         }
         // stage the block (cities and edge lengths, read straight from memory:
         // one barrier, which also orders the previous splice's LDS writes)
-        const tspgpu_city *c2 = blocks + (size_t)(J.first + 1 + m) * L2;
+        const tspgpu_city *c2 = block_at(J.first + 1 + m);
         if (t < L2) {
             const tspgpu_city c = c2[t], d = c2[t + 1 == L2 ? 0 : t + 1];
             cx[t] = c.x, cy[t] = c.y, cid[t] = c.id;
@@ -882,19 +899,41 @@ int host_fold_merge(std::vector<tspgpu_city> &path, const tspgpu_city *c2, int L
     return 0;
 }
 
+// The block paths the core reduces (DEVICE memory): nblocks paths of L cities
+// each at p + b * L, or, with a descriptor table (block_desc.h; the same on
+// the host and on the device), path b of desc[b].L cities at p + desc[b].path.
+struct BlockSet {
+    const tspgpu_city *p = nullptr;
+    int nblocks = 0;
+    int L = 0;                                   // every path's length (no table)
+    const tspgpu::BlockDesc *h_desc = nullptr;   // host
+    const tspgpu::BlockDesc *d_desc = nullptr;   // device
+    size_t total = 0;                            // cities of all paths
+    int max_len = 0;
+    const tspgpu_city *at(int b) const { return p + (h_desc ? (size_t)h_desc[b].path : (size_t)b * L); }
+    int len(int b) const { return h_desc ? h_desc[b].L : L; }
+};
+BlockSet uniform_blocks(const tspgpu_city *p, int L, int nblocks)
+{
+    BlockSet bs;
+    bs.p = p, bs.nblocks = nblocks, bs.L = L, bs.total = (size_t)nblocks * L, bs.max_len = L;
+    return bs;
+}
+
 // The fold of every logical rank (tsp.cpp:348-352) by fold_persist_kernel.
 // Ranks that stall (several near-tied candidates) get the merge exactly on the
 // host and are relaunched from the next one; ranks whose path outgrows LDS
 // finish through the Merger's per-merge kernels.  rank[r] holds the path and
 // rcost[r] the cost on return (costs folded in merge order, tsp.cpp:263, with
 // glibc swap costs of the logged picks).
-int persist_folds(Merger &m, const tspgpu_city *blocks, int L, const double *costs, const std::vector<int> &cnt,
+int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std::vector<int> &cnt,
                   std::vector<DVec> &rank, DVec &tmp, std::vector<double> &rcost)
 {
     const int P = (int)cnt.size();
     int nb = 0;
     for (int c : cnt) nb += c;
-    const size_t ncity = (size_t)nb * L;
+    const size_t ncity = bs.total;
+    const tspgpu_city *blocks = bs.p;
     FoldJob *djobs = nullptr;
     FoldOut *douts = nullptr;
     Pick *dpicks = nullptr;
@@ -927,9 +966,12 @@ int persist_folds(Merger &m, const tspgpu_city *blocks, int L, const double *cos
         std::vector<FoldJob> aj;
         for (int r : active) aj.push_back(jobs[r]);
         e = xcopy_async(djobs, aj.data(), aj.size() * sizeof(FoldJob), hipMemcpyHostToDevice, m.st);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(fold_persist_kernel, dim3((unsigned)aj.size()), dim3(kFoldThreads), 0, m.st, blocks, L,
-                               m.eps2, djobs, douts);
+        if (e == hipSuccess && bs.d_desc)
+            hipLaunchKernelGGL(fold_persist_kernel<true>, dim3((unsigned)aj.size()), dim3(kFoldThreads), 0, m.st,
+                               blocks, 0, bs.d_desc, m.eps2, djobs, douts);
+        else if (e == hipSuccess)
+            hipLaunchKernelGGL(fold_persist_kernel<false>, dim3((unsigned)aj.size()), dim3(kFoldThreads), 0, m.st,
+                               blocks, bs.L, bs.d_desc, m.eps2, djobs, douts);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = xcopy_async(outs.data(), douts, aj.size() * sizeof(FoldOut), hipMemcpyDeviceToHost, m.st);
         if (e == hipSuccess) e = hipStreamSynchronize(m.st);
@@ -948,18 +990,18 @@ int persist_folds(Merger &m, const tspgpu_city *blocks, int L, const double *cos
                 continue;
             }
             // several candidates: merge o.at exactly on the host, then relaunch
-            std::vector<tspgpu_city> path((size_t)o.len), blk((size_t)L);
+            const int sb = firstb[r] + 1 + o.at, Lb = bs.len(sb);  // the stalled merge's block, its own length
+            std::vector<tspgpu_city> path((size_t)o.len), blk((size_t)Lb);
             e = xcopy_async(path.data(), rank[r].p, path.size() * sizeof(tspgpu_city), hipMemcpyDeviceToHost, m.st);
             if (e == hipSuccess)
-                e = xcopy_async(blk.data(), blocks + (size_t)(firstb[r] + 1 + o.at) * L, L * sizeof(tspgpu_city),
-                                   hipMemcpyDeviceToHost, m.st);
+                e = xcopy_async(blk.data(), bs.at(sb), (size_t)Lb * sizeof(tspgpu_city), hipMemcpyDeviceToHost, m.st);
             if (e == hipSuccess) e = hipStreamSynchronize(m.st);
             if (e != hipSuccess) {
                 rc = herr(e);
                 break;
             }
             Cand pk{};
-            rc = host_fold_merge(path, blk.data(), L, pk);
+            rc = host_fold_merge(path, blk.data(), Lb, pk);
             if (rc) break;
             hpick[(size_t)firstb[r] + o.at].c = pk;
             host_picked[(size_t)firstb[r] + o.at] = 1;
@@ -994,7 +1036,7 @@ int persist_folds(Merger &m, const tspgpu_city *blocks, int L, const double *cos
         // the rest of an outgrown rank through the per-merge kernels
         for (int r = 0; r < P && !rc; ++r)
             for (int k = cap_at[r]; k >= 0 && k < cnt[r] - 1 && !rc; ++k)
-                rc = m.merge(rank[r], tmp, &rcost[r], blocks + (size_t)(firstb[r] + 1 + k) * L, L,
+                rc = m.merge(rank[r], tmp, &rcost[r], bs.at(firstb[r] + 1 + k), bs.len(firstb[r] + 1 + k),
                              &costs[firstb[r] + 1 + k], true);
     }
     if (!rc) rc = m.sync();  // (the picks buffer is freed below: nothing in flight may use it)
@@ -1041,15 +1083,16 @@ struct PathDest {
 
 // The core of the reduction (ctx->mu held, the device set): the distribution
 // counts, every logical rank's left fold and the reduction tree over the
-// block paths at `blocks` (DEVICE memory, nblocks paths of L cities; nblocks
-// >= 2), costs on the host.  dmax: the cities' padded bounding-box diagonal;
+// block paths of `bs` (DEVICE memory: nblocks paths of one length or, with a
+// descriptor table, of their own lengths; nblocks >= 2), costs on the host.  dmax: the cities' padded bounding-box diagonal;
 // fold_ok: the paths close on their first city and ids are unique across
 // blocks (the one-kernel fold merges' precondition).  -> *final_cost, the
 // log text, and rank 0's final path into dest (optional).
-int reduce_core(tspgpu_ctx *ctx, const tspgpu_city *blocks, int L, const double *costs, int nblocks, int nprocs,
-                double dmax, bool fold_ok, double *final_cost, std::string &text, const PathDest *dest)
+int reduce_core(tspgpu_ctx *ctx, const BlockSet &bs, const double *costs, int nprocs, double dmax, bool fold_ok,
+                double *final_cost, std::string &text, const PathDest *dest)
 {
-    const size_t ncity = (size_t)nblocks * L;
+    const int nblocks = bs.nblocks;
+    const size_t ncity = bs.total;
     Merger m;
     int rc = m.init(ctx, dmax);
     if (rc) return rc;
@@ -1064,23 +1107,23 @@ int reduce_core(tspgpu_ctx *ctx, const tspgpu_city *blocks, int L, const double 
     std::vector<double> rcost(nprocs, 0.0);
     rc = tmp.reserve(ncity, m.st);
     int next = 0;
-    if (!rc && fold_ok && L <= kFoldL2 && tspgpu::tuned_or("K3_PERSIST", 1) != 0) {
+    if (!rc && fold_ok && bs.max_len <= kFoldL2 && tspgpu::tuned_or("K3_PERSIST", 1) != 0) {
         // (tuning knob K3_PERSIST = 0: the per-merge launches instead; tests compare both)
         // every rank's fold in one persistent launch (fold_persist_kernel)
-        rc = persist_folds(m, blocks, L, costs, cnt, rank, tmp, rcost);
+        rc = persist_folds(m, bs, costs, cnt, rank, tmp, rcost);
         next = nblocks;
     }
     for (int r = 0; r < nprocs && !rc && next < nblocks; ++r) {
         rc = rank[r].reserve(ncity, m.st);
         if (rc) break;
-        rc = herr(xcopy_async(rank[r].p, blocks + (size_t)next * L, L * sizeof(tspgpu_city), hipMemcpyDeviceToDevice,
-                              m.st));
-        rank[r].len = L;
+        rc = herr(xcopy_async(rank[r].p, bs.at(next), (size_t)bs.len(next) * sizeof(tspgpu_city),
+                              hipMemcpyDeviceToDevice, m.st));
+        rank[r].len = (size_t)bs.len(next);
         rcost[r] = costs[next];
         ++next;
         // each logical rank folds its contiguous block range left (tsp.cpp:348-352)
         for (int j = 1; j < cnt[r] && !rc; ++j, ++next)
-            rc = m.merge(rank[r], tmp, &rcost[r], blocks + (size_t)next * L, L, &costs[next], fold_ok);
+            rc = m.merge(rank[r], tmp, &rcost[r], bs.at(next), bs.len(next), &costs[next], fold_ok);
     }
     // MPI_ManualReduce (tsp.cpp:52-134): the receiver appends every received
     // path to one function-local list and merges with the WHOLE list
@@ -1132,16 +1175,25 @@ int reduce_core(tspgpu_ctx *ctx, const tspgpu_city *blocks, int L, const double 
 // The one-kernel fold merges need block tours that close on their first city
 // and ids unique across blocks (the reference's generator numbers cities
 // globally); anything else takes the general path.  The host scan.
-bool host_fold_ok(const tspgpu_city *paths, int L, int nblocks)
+// len: one length per path (concatenated paths), or null: L for every path.
+bool host_fold_ok(const tspgpu_city *paths, int L, const int32_t *len, int nblocks)
 {
-    bool fold_ok = L >= 3;
+    bool fold_ok = true;
+    size_t total = 0;
+    for (int b = 0; b < nblocks && fold_ok; ++b) {  // every path has at least 3 cities
+        const int Lb = len ? len[b] : L;
+        if (Lb < 3) fold_ok = false;
+        total += (size_t)Lb;
+    }
     if (fold_ok) {
         std::vector<int> ids;
-        ids.reserve((size_t)nblocks * (L - 1));
+        ids.reserve(total - (size_t)nblocks);
+        const tspgpu_city *pb = paths;
         for (int b = 0; b < nblocks && fold_ok; ++b) {
-            const tspgpu_city *pb = paths + (size_t)b * L;
-            if (pb[0].id != pb[L - 1].id) fold_ok = false;
-            for (int k = 0; k < L - 1; ++k) ids.push_back(pb[k].id);
+            const int Lb = len ? len[b] : L;
+            if (pb[0].id != pb[Lb - 1].id) fold_ok = false;
+            for (int k = 0; k < Lb - 1; ++k) ids.push_back(pb[k].id);
+            pb += Lb;
         }
         std::sort(ids.begin(), ids.end());
         if (fold_ok && std::adjacent_find(ids.begin(), ids.end()) != ids.end()) fold_ok = false;
@@ -1149,16 +1201,65 @@ bool host_fold_ok(const tspgpu_city *paths, int L, int nblocks)
     return fold_ok;
 }
 
+// The descriptor table of concatenated paths (block_desc.h: path and L; city,
+// dist and n are the caller's) on the host and, uploaded on st, on the device.
+struct DescTable {
+    std::vector<tspgpu::BlockDesc> h;
+    tspgpu::BlockDesc *d = nullptr;
+    ~DescTable()
+    {
+        if (d) (void)hipFree(d);
+    }
+    int upload(hipStream_t st)
+    {
+        hipError_t e = hipMalloc((void **)&d, h.size() * sizeof(tspgpu::BlockDesc));
+        if (e != hipSuccess) {
+            d = nullptr;
+            return herr(e);
+        }
+        // (an H2D copy has read the host table when it returns: xfer.h)
+        return herr(xcopy_async(d, h.data(), h.size() * sizeof(tspgpu::BlockDesc), hipMemcpyHostToDevice, st));
+    }
+    BlockSet blocks(const tspgpu_city *p) const
+    {
+        BlockSet bs;
+        bs.p = p, bs.nblocks = (int)h.size(), bs.h_desc = h.data(), bs.d_desc = d;
+        for (const tspgpu::BlockDesc &e : h) {
+            bs.total += (size_t)e.L;
+            bs.max_len = std::max(bs.max_len, (int)e.L);
+        }
+        return bs;
+    }
+};
+
 // The host front of tspgpu_reduce / tspgpu_reduce_path: argument checks, the
 // three host scans, the upload, then the core.  dest null: no path wanted.
-int reduce_host(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
-                double *final_cost, const PathDest *dest, char *log, int logcap)
+// len (tspgpu_reduce_ragged): the paths are concatenated and path b has len[b]
+// cities; null: nblocks paths of L cities.
+int reduce_host(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const int32_t *len, const double *costs, int nblocks,
+                int nprocs, double *final_cost, const PathDest *dest, char *log, int logcap)
 {
     if (log && logcap > 0) log[0] = 0;
     if (!ctx || !paths || !costs || !final_cost) return -EINVAL;
-    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || L < 2) return -EINVAL;
+    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || (!len && L < 2)) return -EINVAL;
     if (dest && (!dest->len || dest->cap < 0 || (!dest->p && dest->cap > 0))) return -EINVAL;
-    const size_t ncity = (size_t)nblocks * L;
+    size_t ncity = (size_t)nblocks * L;
+    DescTable table;
+    if (len) {
+        ncity = 0;
+        for (int b = 0; b < nblocks; ++b) {
+            if (len[b] < 2) return -EINVAL;
+            ncity += (size_t)len[b];
+        }
+        if (ncity > (size_t)INT_MAX) return -EINVAL;  // (path lengths are ints throughout K3)
+        table.h.resize((size_t)nblocks);
+        int64_t at = 0;
+        for (int b = 0; b < nblocks; ++b) {
+            table.h[b] = tspgpu::BlockDesc{0, 0, at, 0, len[b]};
+            at += len[b];
+        }
+        L = len[0];
+    }
     if (!finite_cities(paths, ncity)) return -EINVAL;
     if (nblocks == 1) {  // one rank, one block: no fold, no tree (nothing to launch or load)
         *final_cost = costs[0];
@@ -1177,10 +1278,11 @@ int reduce_host(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *
     if (!rc) rc = herr(xcopy_async(blocks.p, paths, ncity * sizeof(tspgpu_city), hipMemcpyHostToDevice, ctx->stream));
     if (!rc) rc = herr(hipStreamSynchronize(ctx->stream));
     blocks.len = ncity;
+    if (!rc && len) rc = table.upload(ctx->stream);
     std::string text;
     if (!rc)
-        rc = reduce_core(ctx, blocks.p, L, costs, nblocks, nprocs, dmax, host_fold_ok(paths, L, nblocks), final_cost,
-                         text, dest);
+        rc = reduce_core(ctx, len ? table.blocks(blocks.p) : uniform_blocks(blocks.p, L, nblocks), costs, nprocs, dmax,
+                         host_fold_ok(paths, L, len, nblocks), final_cost, text, dest);
     blocks.release();
     if (rc) return rc;
     put_log(text, log, logcap);
@@ -1237,7 +1339,7 @@ int tspgpu_merge(tspgpu_ctx *ctx, const tspgpu_city *p1, int L1, double c1, cons
 int tspgpu_reduce(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
                   double *final_cost, char *log, int logcap)
 {
-    return reduce_host(ctx, paths, L, costs, nblocks, nprocs, final_cost, nullptr, log, logcap);
+    return reduce_host(ctx, paths, L, nullptr, costs, nblocks, nprocs, final_cost, nullptr, log, logcap);
 }
 
 int tspgpu_reduce_path(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
@@ -1248,20 +1350,64 @@ int tspgpu_reduce_path(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const d
         return -EINVAL;
     }
     const PathDest dest{path_out, false, path_cap, path_len};
-    return reduce_host(ctx, paths, L, costs, nblocks, nprocs, final_cost, &dest, log, logcap);
+    return reduce_host(ctx, paths, L, nullptr, costs, nblocks, nprocs, final_cost, &dest, log, logcap);
 }
 
-int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *d_tour, const double *d_cost,
-                         const int32_t *d_status, int n, int nblocks, int nprocs, double *final_cost,
-                         tspgpu_city *d_path_out, int path_cap, int *path_len, char *log, int logcap, void *hip_stream)
+int tspgpu_reduce_ragged(tspgpu_ctx *ctx, const tspgpu_city *paths, const int32_t *len, const double *costs,
+                         int nblocks, int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap,
+                         int *path_len, char *log, int logcap)
+{
+    if (!path_len || !len) {
+        if (log && logcap > 0) log[0] = 0;
+        return -EINVAL;
+    }
+    const PathDest dest{path_out, false, path_cap, path_len};
+    return reduce_host(ctx, paths, 0, len, costs, nblocks, nprocs, final_cost, &dest, log, logcap);
+}
+
+}  // extern "C"
+
+namespace {
+
+// tspgpu_reduce_device (ns null: n cities and a tour row of n + 1 entries for
+// every block) and tspgpu_reduce_ragged_device (ns: a host array, block b has
+// ns[b] cities packed behind its predecessors', tour rows of tour_stride).
+int reduce_device_front(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *d_tour, int tour_stride,
+                        const double *d_cost, const int32_t *d_status, int n, const int32_t *ns, int nblocks,
+                        int nprocs, double *final_cost, tspgpu_city *d_path_out, int path_cap, int *path_len,
+                        char *log, int logcap, void *hip_stream)
 {
     using tspgpu::PathFacts;
     if (log && logcap > 0) log[0] = 0;
     if (!ctx || !d_cities || !d_tour || !d_cost || !final_cost || !path_len) return -EINVAL;
-    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || n < 2 || n > TSPGPU_MAX_CITIES) return -EINVAL;
+    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs) return -EINVAL;
+    if (!ns && (n < 2 || n > TSPGPU_MAX_CITIES)) return -EINVAL;
     if (path_cap < 0 || (!d_path_out && path_cap > 0)) return -EINVAL;
-    const int L = tspgpu_tour_length(n);
-    const size_t ncity = (size_t)nblocks * L;
+    int L = ns ? 0 : tspgpu_tour_length(n), min_len = L;
+    size_t ncity = (size_t)nblocks * L;
+    DescTable table;
+    if (ns) {
+        // the packed layout is undefined unless every n[b] is in range
+        int max_n = 0;
+        ncity = 0;
+        for (int b = 0; b < nblocks; ++b) {
+            if (ns[b] < 2 || ns[b] > TSPGPU_MAX_CITIES) return -EINVAL;
+            max_n = std::max(max_n, (int)ns[b]);
+            ncity += (size_t)tspgpu_tour_length(ns[b]);
+        }
+        if (tour_stride < max_n + 1) return -EINVAL;
+        table.h.resize((size_t)nblocks);
+        int64_t city = 0, path = 0;
+        min_len = INT_MAX;
+        for (int b = 0; b < nblocks; ++b) {
+            const int Lb = tspgpu_tour_length(ns[b]);
+            table.h[b] = tspgpu::BlockDesc{city, 0, path, ns[b], Lb};
+            city += ns[b];
+            path += Lb;
+            min_len = std::min(min_len, Lb);
+        }
+        L = table.h[0].L;  // (the one-block answer below)
+    }
     if (ncity > (size_t)INT_MAX) return -EINVAL;  // (path lengths are ints throughout K3)
     std::lock_guard<std::mutex> g(ctx->mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return -ENODEV;
@@ -1279,7 +1425,8 @@ int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int
     DVec blocks;
     PathFacts *d_facts = nullptr;
     uint32_t *d_bitmap = nullptr;
-    const size_t bitmap_bytes = (size_t)tspgpu::path_bitmap_bytes(nblocks, L);  // (whole words)
+    // (whole words; for nblocks paths of L cities this is path_bitmap_bytes(nblocks, L))
+    const size_t bitmap_bytes = (size_t)tspgpu::path_bitmap_bytes_total(ncity);
     auto release = [&] {
         blocks.release();
         if (d_facts) (void)hipFree(d_facts);
@@ -1287,7 +1434,8 @@ int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int
     };
     int rc = blocks.reserve(ncity, st);
     if (!rc) rc = herr(hipMalloc((void **)&d_facts, sizeof(PathFacts)));
-    if (!rc && L >= 3) rc = herr(hipMalloc((void **)&d_bitmap, bitmap_bytes));
+    if (!rc && min_len >= 3) rc = herr(hipMalloc((void **)&d_bitmap, bitmap_bytes));
+    if (!rc && ns) rc = table.upload(st);
     // (the timing events are the context's, created on the first call)
     if (!rc && !ctx->ev_k3_gather[0]) rc = herr(hipEventCreate(&ctx->ev_k3_gather[0]));
     if (!rc && !ctx->ev_k3_gather[1]) rc = herr(hipEventCreate(&ctx->ev_k3_gather[1]));
@@ -1298,10 +1446,14 @@ int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int
     if (!rc && d_bitmap) rc = herr(hipMemsetAsync(d_bitmap, 0, bitmap_bytes, st));
     if (!rc) rc = herr(hipEventRecord(ctx->ev_k3_gather[0], st));
     if (!rc)
-        rc = herr(tspgpu::launch_paths_gather(d_cities, d_tour, d_status, n, nblocks, blocks.p, d_facts, grid_cap,
-                                              st));
+        rc = herr(ns ? tspgpu::launch_paths_gather_ragged(d_cities, d_tour, tour_stride, d_status, table.d, nblocks,
+                                                          blocks.p, d_facts, grid_cap, st)
+                     : tspgpu::launch_paths_gather(d_cities, d_tour, d_status, n, nblocks, blocks.p, d_facts, grid_cap,
+                                                   st));
     if (!rc && d_bitmap)
-        rc = herr(tspgpu::launch_paths_unique(blocks.p, L, nblocks, d_bitmap, d_facts, grid_cap, st));
+        rc = herr(ns ? tspgpu::launch_paths_unique_ragged(blocks.p, table.d, nblocks, ncity, d_bitmap, d_facts,
+                                                          grid_cap, st)
+                     : tspgpu::launch_paths_unique(blocks.p, L, nblocks, d_bitmap, d_facts, grid_cap, st));
     if (!rc) rc = herr(hipEventRecord(ctx->ev_k3_gather[1], st));
     // (the D2H copies are complete when they return: xfer.h)
     if (!rc) rc = herr(xcopy_async(&facts, d_facts, sizeof facts, hipMemcpyDeviceToHost, st));
@@ -1326,14 +1478,40 @@ int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int
     } else if (!rc) {
         // the host's own formula over the device's exact extrema: the bits of bbox_diagonal
         const double dmax = tspgpu::path_facts_diagonal(facts);
-        const bool fold_ok = tspgpu::path_facts_fold_ok(facts, L);
+        const bool fold_ok = ns ? tspgpu::path_facts_fold_ok_ragged(facts, min_len) : tspgpu::path_facts_fold_ok(facts, L);
         const PathDest dest{d_path_out, true, path_cap, path_len};
-        rc = reduce_core(ctx, blocks.p, L, costs.data(), nblocks, nprocs, dmax, fold_ok, final_cost, text, &dest);
+        rc = reduce_core(ctx, ns ? table.blocks(blocks.p) : uniform_blocks(blocks.p, L, nblocks), costs.data(), nprocs,
+                         dmax, fold_ok, final_cost, text, &dest);
     }
     release();
     if (rc) return rc;
     put_log(text, log, logcap);
     return *path_len > path_cap ? -ENOSPC : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tspgpu_reduce_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *d_tour, const double *d_cost,
+                         const int32_t *d_status, int n, int nblocks, int nprocs, double *final_cost,
+                         tspgpu_city *d_path_out, int path_cap, int *path_len, char *log, int logcap, void *hip_stream)
+{
+    return reduce_device_front(ctx, d_cities, d_tour, n + 1, d_cost, d_status, n, nullptr, nblocks, nprocs, final_cost,
+                               d_path_out, path_cap, path_len, log, logcap, hip_stream);
+}
+
+int tspgpu_reduce_ragged_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int32_t *n, const int32_t *d_tour,
+                                int tour_stride, const double *d_cost, const int32_t *d_status, int nblocks,
+                                int nprocs, double *final_cost, tspgpu_city *d_path_out, int path_cap, int *path_len,
+                                char *log, int logcap, void *hip_stream)
+{
+    if (!n) {
+        if (log && logcap > 0) log[0] = 0;
+        return -EINVAL;
+    }
+    return reduce_device_front(ctx, d_cities, d_tour, tour_stride, d_cost, d_status, 0, n, nblocks, nprocs, final_cost,
+                               d_path_out, path_cap, path_len, log, logcap, hip_stream);
 }
 
 int tspgpu_reduce_device_last_ms(const tspgpu_ctx *ctx, double *gather_ms)
@@ -1373,6 +1551,54 @@ int tspgpu_pipeline_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, in
         red = tspgpu_reduce_device(ctx, (const tspgpu_city *)d_cities, (const int32_t *)d_tour, (const double *)d_cost,
                                    (const int32_t *)d_status, n, nblocks, nprocs, final_cost, (tspgpu_city *)d_path,
                                    path_cap, path_len, log, logcap, st);
+        if (red == 0 || red == -ENOSPC) {
+            const size_t k = (size_t)std::min(*path_len, path_cap);
+            if (k) rc = tspgpu_memcpy_dtoh(ctx, path_out, d_path, k * sizeof(tspgpu_city));
+        }
+    } else {
+        (void)tspgpu_stream_synchronize(ctx, st);
+    }
+    for (void *p : {d_cities, d_cost, d_tour, d_status, d_path})
+        if (p) (void)tspgpu_device_free(ctx, p);
+    return rc ? rc : red;
+}
+
+int tspgpu_pipeline_cities_ragged(tspgpu_ctx *ctx, const tspgpu_city *cities, const int32_t *n, int nblocks,
+                                  int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len,
+                                  char *log, int logcap)
+{
+    if (log && logcap > 0) log[0] = 0;
+    if (!ctx || !cities || !n || !final_cost || !path_len) return -EINVAL;
+    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs) return -EINVAL;
+    if (path_cap < 0 || (!path_out && path_cap > 0)) return -EINVAL;
+    size_t ncities = 0;
+    int max_n = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        if (n[b] < 2 || n[b] > TSPGPU_MAX_CITIES) return -EINVAL;
+        ncities += (size_t)n[b];
+        max_n = std::max(max_n, (int)n[b]);
+    }
+    // per call, as tspgpu_pipeline_cities: the packed cities, K1's outputs
+    // (tour rows of max n + 1 entries) and the merged tour on the device
+    const int stride = max_n + 1;
+    const size_t ib = ncities * sizeof(tspgpu_city);
+    const size_t tb = (size_t)nblocks * stride * sizeof(int32_t);
+    void *d_cities = nullptr, *d_cost = nullptr, *d_tour = nullptr, *d_status = nullptr, *d_path = nullptr;
+    int rc = tspgpu_device_alloc(ctx, ib, &d_cities);
+    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(double), &d_cost);
+    if (!rc) rc = tspgpu_device_alloc(ctx, tb, &d_tour);
+    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(int32_t), &d_status);
+    if (!rc && path_cap > 0) rc = tspgpu_device_alloc(ctx, (size_t)path_cap * sizeof(tspgpu_city), &d_path);
+    void *st = tspgpu_stream(ctx);
+    if (!rc) rc = tspgpu_memcpy_htod(ctx, d_cities, cities, ib);
+    if (!rc)
+        rc = tspgpu_solve_cities_ragged_device(ctx, (const tspgpu_city *)d_cities, n, nblocks, (double *)d_cost,
+                                               (int32_t *)d_tour, stride, (int32_t *)d_status, st);
+    int red = 0;
+    if (!rc) {
+        red = tspgpu_reduce_ragged_device(ctx, (const tspgpu_city *)d_cities, n, (const int32_t *)d_tour, stride,
+                                          (const double *)d_cost, (const int32_t *)d_status, nblocks, nprocs,
+                                          final_cost, (tspgpu_city *)d_path, path_cap, path_len, log, logcap, st);
         if (red == 0 || red == -ENOSPC) {
             const size_t k = (size_t)std::min(*path_len, path_cap);
             if (k) rc = tspgpu_memcpy_dtoh(ctx, path_out, d_path, k * sizeof(tspgpu_city));

@@ -31,6 +31,7 @@
 
 #include <cstdint>
 
+#include "block_desc.h"
 #include "paths_facts.h"
 #include "tspgpu.h"
 
@@ -48,5 +49,20 @@ hipError_t launch_paths_gather(const tspgpu_city *d_cities, const int32_t *d_tou
 // kPathBadIndex (parts of d_paths are unwritten then).
 hipError_t launch_paths_unique(const tspgpu_city *d_paths, int L, int nblocks, uint32_t *d_bitmap,
                                PathFacts *d_facts, int grid_cap, hipStream_t stream);
+
+// The ragged forms (tspgpu_reduce_ragged_device): block b has
+// d_desc[b].n cities at d_cities + d_desc[b].city, its tour row starts at
+// d_tour + b * tour_stride and its path of d_desc[b].L cities goes to d_paths
+// + d_desc[b].path (block_desc.h; the caller guarantees 2 <= n <= kPathsMaxN,
+// L = tspgpu_tour_length(n) <= tour_stride).  Same facts, same two ordering
+// guarantees.  total: all gathered cities (<= INT_MAX); d_bitmap:
+// path_bitmap_bits_total(total) zeroed bits, whole words.  "Closing copy" is
+// the last city of a block's path.
+hipError_t launch_paths_gather_ragged(const tspgpu_city *d_cities, const int32_t *d_tour, int tour_stride,
+                                      const int32_t *d_status, const BlockDesc *d_desc, int nblocks,
+                                      tspgpu_city *d_paths, PathFacts *d_facts, int grid_cap, hipStream_t stream);
+hipError_t launch_paths_unique_ragged(const tspgpu_city *d_paths, const BlockDesc *d_desc, int nblocks,
+                                      unsigned long long total, uint32_t *d_bitmap, PathFacts *d_facts, int grid_cap,
+                                      hipStream_t stream);
 
 }  // namespace tspgpu

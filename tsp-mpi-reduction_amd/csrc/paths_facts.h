@@ -79,6 +79,19 @@ TSPGPU_PATHS_HD bool path_ids_fit_bitmap(long long id_min, long long id_max, int
     return id_max >= id_min && (unsigned long long)(id_max - id_min) < path_bitmap_bits(nblocks, L);
 }
 
+// The same three for paths of different lengths, over the
+// total count of gathered cities (closing copies included): for nblocks paths
+// of L cities each, total = nblocks * L gives the values above.
+TSPGPU_PATHS_HD unsigned long long path_bitmap_bits_total(unsigned long long total) { return 8ull * total; }
+TSPGPU_PATHS_HD unsigned long long path_bitmap_bytes_total(unsigned long long total)
+{
+    return (path_bitmap_bits_total(total) + 31ull) / 32ull * 4ull;
+}
+TSPGPU_PATHS_HD bool path_ids_fit_bitmap_total(long long id_min, long long id_max, unsigned long long total)
+{
+    return id_max >= id_min && (unsigned long long)(id_max - id_min) < path_bitmap_bits_total(total);
+}
+
 // The diagonal of the bounding box [x0, x1] x [y0, y1], padded: Dmax of K3's
 // candidate window (merge.hip).  One formula for the host scan of
 // tspgpu_reduce and for the extrema the device summary brings, so both give
@@ -112,5 +125,8 @@ inline bool path_facts_fold_ok(const PathFacts &f, int L)
 {
     return L >= 3 && !(f.flags & (kPathOpen | kPathDupId | kPathWideIds));
 }
+// the same for paths of different lengths: EVERY path has at least 3 cities
+// (min_len: the shortest path's length)
+inline bool path_facts_fold_ok_ragged(const PathFacts &f, int min_len) { return path_facts_fold_ok(f, min_len); }
 
 }  // namespace tspgpu

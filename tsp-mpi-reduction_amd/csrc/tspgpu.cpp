@@ -634,6 +634,9 @@ void tspgpu_ctx_release(tspgpu_ctx *c)
     if (c->h_ct_count) (void)hipHostFree(c->h_ct_count);
     if (c->h_rg_desc) (void)hipHostFree(c->h_rg_desc);
     if (c->ev_rg_desc) (void)hipEventDestroy(c->ev_rg_desc);
+    if (c->d_bd_desc) (void)hipFree(c->d_bd_desc);
+    if (c->h_bd_desc) (void)hipHostFree(c->h_bd_desc);
+    if (c->ev_bd_desc) (void)hipEventDestroy(c->ev_bd_desc);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     if (c->ev_k1_done) (void)hipEventDestroy(c->ev_k1_done);
@@ -860,6 +863,10 @@ int tspgpu_stream_destroy(tspgpu_ctx *c, void *stream)
         (void)hipEventSynchronize(c->ev_rg_desc);
         c->rg_desc_pending = false;
     }
+    if (c->bd_desc_pending) {
+        (void)hipEventSynchronize(c->ev_bd_desc);
+        c->bd_desc_pending = false;
+    }
     if (c->k1_last_stream == (hipStream_t)stream) {
         // the next launch must not wait on an event of a destroyed stream's queue:
         // drain it and forget it
@@ -1073,15 +1080,65 @@ int cities_args(const tspgpu_ctx *c, const void *cities, int n, int min_n, int n
     return 0;
 }
 
-// The matrices of nblocks blocks of n cities into d_dist on `stream` (c->mu
-// held).  Synchronises the stream once per build pass; the patch and finish
-// kernels are left running.
+// The descriptor table of packed ragged blocks (block_desc.h) onto the device
+// on `stream`, through the context's pinned buffer (ragged_locked's rule for
+// h_rg_desc).  Blocks of more than skip_above cities get n = 0: the build
+// skips them, the offsets still count them.  -> *out (the context's table).
+int upload_block_desc(tspgpu_ctx *c, const int32_t *ns, int skip_above, int nblocks, hipStream_t stream,
+                      const BlockDesc **out)
+{
+    const size_t bytes = (size_t)nblocks * sizeof(BlockDesc);
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    if ((rc = ensure(&c->d_bd_desc, &c->bd_desc_bytes, bytes))) return rc;
+    if (c->bd_desc_pending) {
+        if ((e = hipEventSynchronize(c->ev_bd_desc)) != hipSuccess) return hip_err(e);
+        c->bd_desc_pending = false;
+    }
+    if (c->h_bd_desc_bytes < bytes) {
+        if (c->h_bd_desc) (void)hipHostFree(c->h_bd_desc);
+        c->h_bd_desc = nullptr;
+        c->h_bd_desc_bytes = 0;
+        if ((e = hipHostMalloc(&c->h_bd_desc, bytes, hipHostMallocDefault)) != hipSuccess) {
+            c->h_bd_desc = nullptr;
+            return hip_err(e);
+        }
+        c->h_bd_desc_bytes = bytes;
+    }
+    if (!c->ev_bd_desc && (e = hipEventCreateWithFlags(&c->ev_bd_desc, hipEventDisableTiming)) != hipSuccess)
+        return hip_err(e);
+    BlockDesc *hd = static_cast<BlockDesc *>(c->h_bd_desc);
+    int64_t city = 0, dist = 0, path = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        const int k = ns[b], L = tspgpu_tour_length(k);
+        hd[b] = BlockDesc{city, dist, path, k > skip_above ? 0 : k, L};
+        city += k;
+        dist += (int64_t)k * k;
+        path += L;
+    }
+    if ((e = hipMemcpyAsync(c->d_bd_desc, hd, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return hip_err(e);
+    if ((e = hipEventRecord(c->ev_bd_desc, stream)) != hipSuccess) return hip_err(e);
+    c->bd_desc_pending = true;
+    *out = static_cast<const BlockDesc *>(c->d_bd_desc);
+    return 0;
+}
+
+// The matrices of nblocks blocks into d_dist on `stream` (c->mu held): n
+// cities each, or, with ns (a host array, every entry in [1, 20]), packed
+// ragged blocks of ns[b] cities (those above skip_above are not built).
+// Synchronises the stream once per build pass; the patch and finish kernels
+// are left running.
 int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
-                        hipStream_t stream)
+                        hipStream_t stream, const int32_t *ns = nullptr, int skip_above = TSPGPU_MAX_CITIES)
 {
     using clk = std::chrono::steady_clock;
     if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
-    const unsigned long long squares = (unsigned long long)nblocks * n * (n - 1);
+    unsigned long long squares = (unsigned long long)nblocks * n * (n - 1);
+    if (ns) {
+        squares = 0;
+        for (int b = 0; b < nblocks; ++b)
+            if (ns[b] <= skip_above) squares += (unsigned long long)ns[b] * (ns[b] - 1);
+    }
     // list capacity: a quarter of the squares (the rule flags a tenth of the
     // generator's), or the test knob; an overflowing build is run again
     unsigned long long cap = squares / 4;
@@ -1104,6 +1161,8 @@ int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int n
     if (c->k1_launched && stream != c->k1_last_stream) {
         if ((e = hipStreamWaitEvent(stream, c->ev_k1_done, 0)) != hipSuccess) return hip_err(e);
     }
+    const BlockDesc *desc = nullptr;
+    if (ns && (rc = upload_block_desc(c, ns, skip_above, nblocks, stream, &desc))) return rc;
     const auto t0 = clk::now();
     unsigned long long count = 0;
     int passes = 0;
@@ -1126,7 +1185,10 @@ int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int n
         }
         e = hipMemsetAsync(c->d_ct_count, 0, sizeof(unsigned long long), stream);
         if (e == hipSuccess)
-            e = launch_cities_build(d_cities, n, nblocks, d_dist, c->d_ct_slot, c->d_ct_dx, cap, c->d_ct_count, stream);
+            e = desc ? launch_cities_build_ragged(d_cities, desc, nblocks, d_dist, c->d_ct_slot, c->d_ct_dx, cap,
+                                                  c->d_ct_count, stream)
+                     : launch_cities_build(d_cities, n, nblocks, d_dist, c->d_ct_slot, c->d_ct_dx, cap, c->d_ct_count,
+                                           stream);
         if (e == hipSuccess)
             e = hipMemcpyAsync(c->h_ct_count, c->d_ct_count, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                stream);
@@ -1159,7 +1221,9 @@ int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int n
     if (count)
         e = hipMemcpyAsync(c->d_ct_dx, v, (size_t)count * sizeof(double), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = launch_cities_patch(d_dist, c->d_ct_slot, c->d_ct_dx, count, stream);
-    if (e == hipSuccess) e = launch_cities_finish(n, nblocks, d_dist, stream);
+    if (e == hipSuccess)
+        e = desc ? launch_cities_finish_ragged(desc, nblocks, d_dist, stream)
+                 : launch_cities_finish(n, nblocks, d_dist, stream);
     if (e == hipSuccess) e = hipEventRecord(c->ev_k1_done, stream);
     if (e != hipSuccess) return hip_err(e);
     c->k1_last_stream = stream;
@@ -1189,9 +1253,112 @@ int cities_solve_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int n
     return ragged_locked(c, c->d_ct_dist, 8, plan, 0, d_cost, d_tour, n + 1, d_status, stream);
 }
 
+// The call-level checks of the packed ragged city forms,
+// before the context is touched; 1: nothing to do (nblocks == 0).  Every
+// n[b] must be in [min_n, TSPGPU_MAX_CITIES]: the packed layout is undefined
+// otherwise.  -> *max_n, *ncities.
+int cities_ragged_args(const tspgpu_ctx *c, const void *cities, const int32_t *n, int nblocks, int min_n, int *max_n,
+                       int64_t *ncities)
+{
+    if (!c || nblocks < 0) return -EINVAL;
+    if (nblocks == 0) return 1;
+    if (!cities || !n) return -EINVAL;
+    int m = 0;
+    int64_t total = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        if (n[b] < min_n || n[b] > TSPGPU_MAX_CITIES) return -EINVAL;
+        m = std::max(m, (int)n[b]);
+        total += n[b];
+    }
+    *max_n = m;
+    *ncities = total;
+    return 0;
+}
+
+// build the packed matrices into the context's buffer, then the ragged path
+// with the packed offsets (c->mu held).  On a strict context a block of 17..20
+// cities is refused by the plan (status -EINVAL) and its matrix is not built.
+int cities_ragged_solve_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, const int32_t *n, int nblocks,
+                               double *d_cost, int32_t *d_tour, int tour_stride, int32_t *d_status, hipStream_t stream)
+{
+    std::vector<int64_t> offset((size_t)nblocks);
+    int64_t elems = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        offset[b] = elems;
+        elems += (int64_t)n[b] * n[b];
+    }
+    RaggedPlan plan;
+    int rc = ragged_plan(n, offset.data(), nblocks, c->strict, 8, &plan);
+    if (rc) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    if ((rc = ensure(&c->d_ct_dist, &c->ct_dist_bytes, (size_t)elems * sizeof(double)))) return rc;
+    const int skip_above = c->strict ? TSPGPU_REFERENCE_MAX_CITIES : TSPGPU_MAX_CITIES;
+    if ((rc = cities_build_locked(c, d_cities, 0, nblocks, c->d_ct_dist, stream, n, skip_above))) return rc;
+    return ragged_locked(c, c->d_ct_dist, 8, plan, 0, d_cost, d_tour, tour_stride, d_status, stream);
+}
+
 }  // namespace
 
 extern "C" {
+
+int tspgpu_distance_matrix_ragged_device(tspgpu_ctx *c, const tspgpu_city *d_cities, const int32_t *n, int nblocks,
+                                         double *d_dist, void *hip_stream)
+{
+    int max_n = 0;
+    int64_t ncities = 0;
+    const int rc = cities_ragged_args(c, d_cities, n, nblocks, 1, &max_n, &ncities);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!d_dist) return -EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return cities_build_locked(c, d_cities, 0, nblocks, d_dist, (hipStream_t)hip_stream, n);
+}
+
+int tspgpu_solve_cities_ragged_device(tspgpu_ctx *c, const tspgpu_city *d_cities, const int32_t *n, int nblocks,
+                                      double *d_cost, int32_t *d_tour, int tour_stride, int32_t *d_status,
+                                      void *hip_stream)
+{
+    int max_n = 0;
+    int64_t ncities = 0;
+    const int rc = cities_ragged_args(c, d_cities, n, nblocks, 2, &max_n, &ncities);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!d_cost || !d_tour || !d_status || tour_stride < max_n + 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    return cities_ragged_solve_locked(c, d_cities, n, nblocks, d_cost, d_tour, tour_stride, d_status,
+                                      (hipStream_t)hip_stream);
+}
+
+int tspgpu_solve_cities_ragged(tspgpu_ctx *c, const tspgpu_city *cities, const int32_t *n, int nblocks,
+                               double *cost_out, int32_t *tour_out, int tour_stride, int32_t *status_out)
+{
+    int max_n = 0;
+    int64_t ncities = 0;
+    int rc = cities_ragged_args(c, cities, n, nblocks, 2, &max_n, &ncities);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!cost_out || !tour_out || !status_out || tour_stride < max_n + 1) return -EINVAL;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
+    const size_t ib = (size_t)ncities * sizeof(tspgpu_city);
+    const size_t cb = (size_t)nblocks * sizeof(double);
+    const size_t tb = (size_t)nblocks * tour_stride * sizeof(int32_t);
+    const size_t sb = (size_t)nblocks * sizeof(int32_t);
+    if ((rc = ensure(&c->d_ct_cities, &c->ct_cities_bytes, ib))) return rc;
+    if ((rc = ensure(&c->d_cost, &c->cost_bytes, cb))) return rc;
+    if ((rc = ensure(&c->d_tour, &c->tour_bytes, tb))) return rc;
+    if ((rc = ensure(&c->d_rg_ostatus, &c->rg_ostatus_bytes, sb))) return rc;
+    hipError_t e = xcopy_async(c->d_ct_cities, cities, ib, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return hip_err(e);
+    rc = cities_ragged_solve_locked(c, c->d_ct_cities, n, nblocks, c->d_cost, c->d_tour, tour_stride, c->d_rg_ostatus,
+                                    c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // (the caller's cities may go once this returns)
+        return rc;
+    }
+    e = xcopy_async(cost_out, c->d_cost, cb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = xcopy_async(tour_out, c->d_tour, tb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = xcopy_async(status_out, c->d_rg_ostatus, sb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return hip_err(e);  // (0 however many blocks are bad: status_out says which)
+}
 
 int tspgpu_distance_matrix_device(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
                                   void *hip_stream)

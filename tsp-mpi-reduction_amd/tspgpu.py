@@ -47,6 +47,9 @@ EXPORTED_SYMBOLS = (
     # distances on the device (cities in device memory, the host's pow on the flagged squares only)
     "tspgpu_distance_matrix_device", "tspgpu_solve_cities_device", "tspgpu_solve_cities_upload",
     "tspgpu_cities_last_fixups", "tspgpu_cities_last_phase_ms",
+    # ragged blocks end to end: packed cities of different block sizes -> distances, K1, K3, the merged tour
+    "tspgpu_distance_matrix_ragged_device", "tspgpu_solve_cities_ragged_device", "tspgpu_solve_cities_ragged",
+    "tspgpu_reduce_ragged_device", "tspgpu_reduce_ragged", "tspgpu_pipeline_cities_ragged",
     # tuning / test knobs
     "tspgpu_tuning_set", "tspgpu_tuning_clear",
 )
@@ -212,6 +215,15 @@ def lib():
         L.tspgpu_reduce_device_last_ms.argtypes = [vp, dp]
         L.tspgpu_pipeline_cities.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, cp, ctypes.c_int,
                                              intp, ctypes.c_char_p, ctypes.c_int]
+        L.tspgpu_distance_matrix_ragged_device.argtypes = [vp, vp, ip, ctypes.c_int, vp, vp]
+        L.tspgpu_solve_cities_ragged_device.argtypes = [vp, vp, ip, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]
+        L.tspgpu_solve_cities_ragged.argtypes = [vp, cp, ip, ctypes.c_int, dp, ip, ctypes.c_int, ip]
+        L.tspgpu_reduce_ragged_device.argtypes = [vp, vp, ip, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, dp,
+                                                  vp, ctypes.c_int, intp, ctypes.c_char_p, ctypes.c_int, vp]
+        L.tspgpu_reduce_ragged.argtypes = [vp, cp, ip, dp, ctypes.c_int, ctypes.c_int, dp, cp, ctypes.c_int, intp,
+                                           ctypes.c_char_p, ctypes.c_int]
+        L.tspgpu_pipeline_cities_ragged.argtypes = [vp, cp, ip, ctypes.c_int, ctypes.c_int, dp, cp, ctypes.c_int,
+                                                    intp, ctypes.c_char_p, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -277,6 +289,20 @@ def cities_array(blocks):
             c = arr[b * n + j]
             c.id, c.x, c.y = int(cid), float(x), float(y)
     return arr, n, B
+
+
+def cities_array_ragged(blocks):
+    """blocks of different sizes, each a list of (id, x, y) -> (ctypes City
+    array of the packed cities in block order, n (B,) int32)."""
+    ns = np.array([len(blk) for blk in blocks], dtype=np.int32)
+    arr = (City * max(1, int(ns.sum())))()
+    k = 0
+    for blk in blocks:
+        for cid, x, y in blk:
+            c = arr[k]
+            c.id, c.x, c.y = int(cid), float(x), float(y)
+            k += 1
+    return arr, ns
 
 
 def distance_matrix(blocks) -> np.ndarray:
@@ -694,6 +720,109 @@ class Context:
 
         return self._path_result("tspgpu_pipeline_cities", call, path_cap,
                                  self._tour_capacity(B, tour_length(n), nprocs))
+
+    # ---- ragged blocks end to end (packed cities, blocks of different sizes) ----
+
+    @staticmethod
+    def _ns(n):
+        return np.ascontiguousarray(n, dtype=np.int32)
+
+    def distance_matrix_ragged_device(self, d_cities_ptr: int, n, d_dist_ptr: int, stream_ptr: int = 0):
+        """tspgpu_distance_matrix_ragged_device: packed cities (block b has n[b],
+        a host array) -> the packed matrices (block b at sum n[a]^2) at
+        d_dist_ptr, each with the bits of distance_matrix() on that block."""
+        n = self._ns(n)
+        rc = lib().tspgpu_distance_matrix_ragged_device(self.handle, d_cities_ptr, _ip(n), len(n), d_dist_ptr,
+                                                        stream_ptr or None)
+        if rc:
+            raise TspGpuError(rc, "tspgpu_distance_matrix_ragged_device")
+
+    def solve_cities_ragged_device(self, d_cities_ptr: int, n, d_cost_ptr: int, d_tour_ptr: int, tour_stride: int,
+                                   d_status_ptr: int, stream_ptr: int = 0):
+        """tspgpu_solve_cities_ragged_device: packed cities on the device -> cost
+        (B float64), tours (B x tour_stride int32) and status (B int32) on the
+        device, under the ragged contract."""
+        n = self._ns(n)
+        rc = lib().tspgpu_solve_cities_ragged_device(self.handle, d_cities_ptr, _ip(n), len(n), d_cost_ptr, d_tour_ptr,
+                                                     tour_stride, d_status_ptr, stream_ptr or None)
+        if rc:
+            raise TspGpuError(rc, "tspgpu_solve_cities_ragged_device")
+
+    def solve_cities_ragged(self, blocks, tour_stride: int | None = None):
+        """tspgpu_solve_cities_ragged: blocks of different sizes (lists of
+        (id, x, y), or a (ctypes City array, n) pair from cities_array_ragged)
+        -> (cost (B,), tours (B, tour_stride) padded with -1, status (B,)).
+        tour_stride None: the largest n + 1."""
+        arr, n = blocks if isinstance(blocks, tuple) else cities_array_ragged(blocks)
+        n = self._ns(n)
+        B = len(n)
+        if tour_stride is None:
+            tour_stride = int(n.max()) + 1 if B else 1
+        cost = np.zeros(B, dtype=np.float64)
+        tour = np.full((B, tour_stride), -1, dtype=np.int32)
+        status = np.zeros(B, dtype=np.int32)
+        rc = lib().tspgpu_solve_cities_ragged(self.handle, arr, _ip(n), B, _dp(cost), _ip(tour), tour_stride,
+                                              _ip(status))
+        if rc:
+            raise TspGpuError(rc, "tspgpu_solve_cities_ragged")
+        return cost, tour, status
+
+    def reduce_ragged_device(self, d_cities_ptr: int, n, d_tour_ptr: int, tour_stride: int, d_cost_ptr: int,
+                             d_status_ptr: int, nprocs: int, d_path_ptr: int = 0, path_cap: int = 0,
+                             stream_ptr: int = 0):
+        """tspgpu_reduce_ragged_device: the outputs of solve_cities_ragged_device
+        reduced without a visit to the host -> (final cost, log text, full
+        path length); the merged tour goes to d_path_ptr.  A path_cap below
+        the length raises -ENOSPC with cost, log and path_len on the error."""
+        n = self._ns(n)
+        final, plen = ctypes.c_double(), ctypes.c_int(-1)
+        log = ctypes.create_string_buffer(1 << 20)
+        rc = lib().tspgpu_reduce_ragged_device(self.handle, d_cities_ptr, _ip(n), d_tour_ptr, tour_stride, d_cost_ptr,
+                                               d_status_ptr or None, len(n), nprocs, ctypes.byref(final),
+                                               d_path_ptr or None, path_cap, ctypes.byref(plen), log, len(log),
+                                               stream_ptr or None)
+        if rc:
+            err = TspGpuError(rc, "tspgpu_reduce_ragged_device")
+            err.path_len, err.cost, err.log = plen.value, final.value, log.value.decode()
+            raise err
+        return final.value, log.value.decode(), plen.value
+
+    def reduce_ragged(self, paths, costs, nprocs: int, path_cap: int | None = None):
+        """tspgpu_reduce_ragged: paths of different lengths (B lists of >= 2
+        cities), costs (B,) -> (final cost, log text, rank 0's final path);
+        path_cap as for reduce_path."""
+        flat, lens = cities_array_ragged(paths)
+        c = np.ascontiguousarray(costs, dtype=np.float64)
+        B = len(lens)
+
+        def call(out, cap):
+            final, plen = ctypes.c_double(), ctypes.c_int(-1)
+            log = ctypes.create_string_buffer(1 << 20)
+            rc = lib().tspgpu_reduce_ragged(self.handle, flat, _ip(lens), _dp(c), B, nprocs, ctypes.byref(final), out,
+                                            cap, ctypes.byref(plen), log, len(log))
+            return rc, final.value, log.value.decode(), plen.value
+
+        return self._path_result("tspgpu_reduce_ragged", call, path_cap,
+                                 self._tour_capacity(1, int(lens.sum()), nprocs))
+
+    def pipeline_cities_ragged(self, blocks, nprocs: int, path_cap: int | None = None):
+        """tspgpu_pipeline_cities_ragged: blocks of different sizes (lists of
+        (id, x, y), or a (ctypes City array, n) pair) -> (final cost, log
+        text, merged tour as a list of (id, x, y)); path_cap as for
+        pipeline_cities."""
+        arr, n = blocks if isinstance(blocks, tuple) else cities_array_ragged(blocks)
+        n = self._ns(n)
+        total = int(sum(tour_length(int(k)) for k in n))
+
+        def call(out, cap):
+            final, plen = ctypes.c_double(), ctypes.c_int(-1)
+            log = ctypes.create_string_buffer(1 << 20)
+            rc = lib().tspgpu_pipeline_cities_ragged(self.handle, arr, _ip(n), len(n), nprocs, ctypes.byref(final), out,
+                                                     cap, ctypes.byref(plen), log, len(log))
+            return rc, final.value, log.value.decode(), plen.value
+
+        return self._path_result("tspgpu_pipeline_cities_ragged", call, path_cap,
+                                 self._tour_capacity(1, total, nprocs))
 
     def device_info(self):
         cu = ctypes.c_int()
