@@ -30,6 +30,10 @@
 //   host-built entry (sub_rows.h; global, L2-resident), prefetched one pass
 //   ahead; decoding is independent shift/mask ops instead of a dependent ctz
 //   chain, two per store slot.
+// Shapes: L = 10 on 256-thread workgroups, six per CU (eight for i32), and,
+// the 16-city f64 default, L = 11 on 512-thread workgroups, three per CU —
+// the same 24 waves per CU, 20% fewer pushed entries, half the sub-cubes
+// (k1_cfg.h).
 #pragma once
 #include "hk_tiled.h"
 #include "sub_rows.h"
@@ -60,7 +64,7 @@ __host__ __device__ constexpr int sub_layer_off(int L, int j)
 {
     return (j & 1) ? tiled_region_vals(L) - tiled_layer_vals(L, j) : 0;
 }
-// Overlapped edge passes (256-thread workgroups): passes 0/1 of sub-cube h + 1
+// Overlapped edge passes (workgroups of 256 threads or more): passes 0/1 of sub-cube h + 1
 // run during the last middle pass of h and pass L of h during the first middle
 // pass of h + 1, on the waves those passes leave idle; the push values of
 // passes 0/1, L - 1 and L are staged into LDS one pass earlier — the separate
@@ -85,7 +89,7 @@ struct SubCtx {
     V *pst;            // pass L-1's push values staged in LDS (overlapped edge passes): [row][i]
     V *fst;            // passes 0/1's push values: [i] row 0, [H + a*H + i] row {a}
     V *lst;            // pass L's push values: [i]
-    int ov;            // 2: overlapped edge passes (256-thread workgroups), 0: separate edge intervals
+    int ov;            // 2: overlapped edge passes (256 threads or more), 0: separate edge intervals
     Rsrc<V> push;      // this block's push area
     Rsrc<uint64_t> par;  // this block's parent words
 };
@@ -179,13 +183,24 @@ __device__ __forceinline__ uint32_t sub_nib(const uint4 &e, int i)
 {
     return i < 8 ? (e.x >> (4 * i)) & 15u : (e.y >> (4 * (i - 8))) & 15u;
 }
-// the finished slot of the q-th low destination in the next low layer (sub_rows.h)
+__device__ __forceinline__ uint32_t sub_word(const uint4 &e, int i)
+{
+    return i == 0 ? e.x : (i == 1 ? e.y : (i == 2 ? e.z : e.w));
+}
+// the finished slot of the q-th low destination in the next low layer
+// (sub_rows.h): the entry's field — read from two words where the layout of
+// (L, J) lets it straddle them — plus, where the field keeps the rank only,
+// the layer offset of the destination's position k_q - q (k_q = nibble J + q)
 template <int L, int J>
 __device__ __forceinline__ uint32_t sub_slot(const uint4 &e, int q)
 {
+    constexpr int bits = sub_slot_bits(L, J);
     const int pos = sub_slot_pos(L, J, q);
-    const uint32_t w = pos < 32 ? e.x : (pos < 64 ? e.y : (pos < 96 ? e.z : e.w));
-    return (w >> (pos & 31)) & ((1u << sub_slot_bits(L, J)) - 1u);
+    uint32_t v = sub_word(e, pos / 32) >> (pos & 31);
+    if ((pos & 31) + bits > 32) v |= sub_word(e, pos / 32 + 1) << (32 - (pos & 31));
+    v &= (1u << bits) - 1u;
+    if constexpr (sub_slot_rank_only(L, J)) v += (sub_nib(e, J + q) - (uint32_t)q) * (uint32_t)sub_binom(L, J + 1);
+    return v;
 }
 
 // ---------------------------------------------------------------------------
@@ -761,13 +776,15 @@ __global__ __launch_bounds__(THREADS, tiled_waves(THREADS, WG)) void hk_sub_kern
     constexpr int n = N + 1;
     constexpr int VB = sizeof(V);
     constexpr uint32_t DSB = (uint32_t)(sub_ds(L) * VB);
-    static_assert(H >= 1 && H <= 6 && L >= 5 && L <= 10, "variant 6 sizes");
+    static_assert(H >= 1 && H <= 6 && L >= kSubRowMinL && L <= kSubRowMaxL, "variant 6 sizes");
     static_assert(sub_ds(L) >= N + H, "image stride");
     // a middle pass gives each of its rows a thread; the edge intervals loop
-    // their virtual lanes (pass 0/1 lanes 0..191, pass L 192..; pass L-1
-    // lanes 0..127, the next sub-cube's image rows 128..) over the workgroup
+    // their 256 virtual lanes (pass 0/1 lanes 0..191, pass L 192..; pass L-1
+    // lanes 0..127, the next sub-cube's image rows 128..) over the workgroup:
+    // two turns at 128 threads, one at 256 and above (lanes past 255 idle)
     static_assert(THREADS % 64 == 0 && THREADS >= cbinom(L, L / 2), "one row per thread in a middle pass");
-    static_assert(L * (N - 1) + H <= 192 && L * 8 <= 128, "edge intervals: virtual lane layout");
+    static_assert(L * (N - 1) + H <= 192 && L * 8 <= 128 && H * L + (H / 2) * (H - H / 2) <= 128,
+                  "edge intervals: virtual lane layout");
     // static LDS: image/region offsets fold into immediates (A/B against
     // dynamic LDS: equal within noise, profiles/r03/k1_ab_table.log)
     __shared__ __attribute__((aligned(16))) char smem[sub_lds_bytes(N, L, VB)];
@@ -778,8 +795,8 @@ __global__ __launch_bounds__(THREADS, tiled_waves(THREADS, WG)) void hk_sub_kern
     c.d0 = d0;
     c.region = dc + 16;
     c.layerL = c.region + sub_region_vals(L);
-    // (the overlapped edge passes need the idle waves of a 256-thread workgroup)
-    constexpr int OV = THREADS == 256 ? 2 : 0;
+    // (the overlapped edge passes need the idle waves 1..3 of a workgroup of 256 threads or more)
+    constexpr int OV = THREADS >= 256 ? 2 : 0;
     c.ov = OV;
     c.layer2 = OV ? c.layerL + 16 : c.region + sub_layer_off(L, 2);
     c.pst = c.layerL + 16 + sub_l2_vals(L);
@@ -842,8 +859,17 @@ __global__ __launch_bounds__(THREADS, tiled_waves(THREADS, WG)) void hk_sub_kern
                 }
                 sub_dispatch_mid_j<V, N, L, j>(c, h, hc, tj, cur);
                 if constexpr (OV) {
-                    // edge passes on the waves this middle pass leaves idle
-                    static_assert(cbinom(L, 2) <= 64 && cbinom(L, 3) <= 128 && cbinom(L, L - 3) <= 128, "overlap: idle waves");
+                    // edge passes on waves that have no row in the middle pass
+                    // they run beside, the same waves at every workgroup size:
+                    // passes 2 and L - 2 have their rows on wave 0 (C(L, 2) <=
+                    // 64) and leave waves 1-3 to the three staging steps and to
+                    // passes 0/1 of h + 1 (192 lanes); pass 3 has its rows on
+                    // waves 0-2 at most (C(L, 3) <= 192: 120 rows at L = 10, 165
+                    // at L = 11) and leaves wave 3 to pass L of h - 1.  (Waves 4-7
+                    // of a 512-thread workgroup have rows in passes 4..L - 4 only.)
+                    static_assert(THREADS >= 256 && cbinom(L, 2) <= 64 && cbinom(L, 3) <= 192, "overlap: idle waves");
+                    static_assert(L * (N - 1) + H <= 192 && L * H <= 64 && H + L * H <= 64,
+                                  "overlap: the edge work fits its waves");
                     // pass 2: the edge passes' push values into LDS (waves 1-3);
                     // pass 3: pass L of h - 1 from them (wave 3)
                     if constexpr (j == 2) {

@@ -19,7 +19,9 @@
 // sub-cube h.  At n = 16 with the default L = 10 (N = 15, H = 5) that is
 // 81,920 of the block's 245,760 entries: 1.31 MB of table traffic per block
 // instead of 3.93 MB (SURVEY.md §8(d)'s compulsory bytes of the
-// layer-by-layer form).
+// layer-by-layer form).  With L = 11 (H = 4: the 16-city f64 default since
+// configuration 65 of k1_cfg.h) it is 65,536 entries, 64 push columns of 2048
+// rows, and the two live low layers take 40 KB.
 //
 // Slot of one block (global memory, tiled_slot_bytes): the push area
 // [h][high city][row], the parent words [h][row] and the backtracking's

@@ -2,6 +2,9 @@
 //   X(id, value type, N, L, threads, workgroups/CU)
 // The first row per (N, value type) is the default; TSPGPU_TILED_CFG picks
 // another by id.  A new row needs a matching k1/hks_p<id>.hip.
+// 16 cities f64: 65 (eleven low cities, 512-thread workgroups) is 3.7% faster
+// than 60 per 65536 blocks (profiles/l11_v6); 60 stays
+// selectable.
 //
 // tests/test_k1_variants_gpu.py lists the configurations by reading this
 // file: it finds a table by its #define line and takes the rows up to the
@@ -15,6 +18,7 @@
 #define TSPGPU_TILED_PRODUCT_CFGS(X) /* variant 5: retired, no rows */
 
 #define TSPGPU_SUB_PRODUCT_CFGS(X) \
+    X(65, double, 15, 11, 512, 3) \
     X(60, double, 15, 10, 256, 6) \
     X(61, int32_t, 15, 10, 256, 8) \
     X(62, double, 14, 10, 256, 6) \

@@ -23,7 +23,11 @@ bool build_sub_rows(int L, std::vector<SubRow> &rows)
         const uint32_t m = order[i];
         const int J = __builtin_popcount(m);
         SubRow e = {{0u, 0u, 0u, 0u}};
-        auto put = [&](int pos, uint32_t v) { e.w[pos / 32] |= v << (pos % 32); };
+        // (a field that straddles two words, layouts 1 and 3: its high bits go to the next word)
+        auto put = [&](int pos, uint32_t v) {
+            e.w[pos / 32] |= v << (pos % 32);
+            if (pos % 32 && (v >> (32 - pos % 32))) e.w[pos / 32 + 1] |= v >> (32 - pos % 32);
+        };
         int nib = 0;
         for (int b = 0; b < L; ++b)
             if (m >> b & 1) put(4 * nib++, (uint32_t)b);
@@ -31,8 +35,10 @@ bool build_sub_rows(int L, std::vector<SubRow> &rows)
         for (int b = 0; b < L; ++b)
             if (!(m >> b & 1)) {
                 put(4 * nib++, (uint32_t)b);
-                if (sub_row_has_slots(L, J))
-                    put(sub_slot_pos(L, J, q), (uint32_t)((b - q) * sub_binom(L, J + 1) + rank[m | (1u << b)]));
+                if (sub_row_has_slots(L, J)) {
+                    const int layer_off = sub_slot_rank_only(L, J) ? 0 : (b - q) * sub_binom(L, J + 1);
+                    put(sub_slot_pos(L, J, q), (uint32_t)(layer_off + rank[m | (1u << b)]));
+                }
                 ++q;
             }
         rows[i] = e;

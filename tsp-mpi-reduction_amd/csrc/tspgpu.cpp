@@ -190,8 +190,9 @@ int ensure_tiled_info(tspgpu_ctx *c, int L)
     return 0;
 }
 
-// Variant 6 keeps one global slot per block of a launch (1.65 MB at
-// n = 16) until its backtracking kernel has run, so a launch takes blocks in
+// Variant 6 keeps one global slot per block of a launch (sized by the
+// configuration in use: 1.65 MB at n = 16 with ten low cities, 1.49 MB with
+// eleven) until its backtracking kernel has run, so a launch takes blocks in
 // chunks: up to 65536 (108 GB of the 288 GB at n = 16 — a persistent grid of
 // 1536 workgroups then idles a third of the chip for 0.67 of 42.7 rounds
 // instead of 0.67 of 10.7 at 16384), at most 3/4 of the device memory free
