@@ -1,6 +1,8 @@
 """K1-wide (csrc/hkwide.hip): one instance's Held-Karp over the whole GPU.
 Same bits and tour as the reference (goldens), the oracle and K1; past K1's
-sizes (n = 21, 22) it must agree with K2, an independent exact algorithm."""
+sizes it must agree with K2, an independent exact algorithm: n = 21, 22 here,
+n = 23 .. 31 (the oracle's stored answers to 26, then K2) in
+tests/test_wide_large_gpu.py."""
 import numpy as np
 import pytest
 
