@@ -13,16 +13,31 @@
  * Return codes: 0 on success, otherwise a negative errno value
  *   -EINVAL  bad argument (n outside [2, TSPGPU_MAX_CITIES] (strict: 16), nblocks < 0,
  *            NULL pointer, non-finite or negative distance; -0.0 counts as
- *            negative: a minimum over zeros of both signs has no defined sign)
+ *            negative: a minimum over zeros of both signs has no defined sign;
+ *            (K3) a non-finite coordinate, see K3's coordinate domain below)
  *   -ERANGE  n * max(d) >= INT_MAX: the reference's INT_MAX sentinel
  *            (tsp.cpp:411,453) would leave its tour undefined
  *   -ENODEV  no HIP device / device ordinal out of range
  *   -ENOMEM  device allocation failed
- *   -EIO     a HIP runtime call or kernel launch failed
+ *   -EIO     a HIP runtime call or kernel launch failed; (K3) no swap cost below
+ *            INT_MAX, see K3's coordinate domain below
  *   -EDEADLK (K3) the reference's mergeBlocks would never terminate for these paths
- *            (its rotation loop, tsp.cpp:236-239, looks for a city that is not there)
+ *            (its rotation loop, tsp.cpp:236-239, looks for a city that is not there);
+ *            promised, like every K3 answer, inside K3's coordinate domain below
  *   -ENOSPC  (K3) the merged tour is longer than path_cap (everything else was written)
  *   -EOVERFLOW (K2) more optimal tours than can be enumerated, n > 31
+ *
+ * K3's coordinate domain (tspgpu_merge, every tspgpu_reduce* and
+ * tspgpu_pipeline* form).  The reference's pair, cost and path are promised
+ * where
+ *   (1) every coordinate is finite (else -EINVAL);
+ *   (2) the square of every coordinate difference is zero or lies in
+ *       [2^-900, 2^1000]: the device's dx*dx then neither underflows nor
+ *       overflows against the host's pow (not checked);
+ *   (3) the minimum swap cost of every merge is below INT_MAX, the value the
+ *       reference's search starts from (above it the reference's own result
+ *       is undefined; the call may return -EIO).
+ * Sign, translation and power-of-two scale inside (2) are free.
  */
 #ifndef TSPGPU_H
 #define TSPGPU_H
