@@ -18,7 +18,7 @@ later chunk's block uses slot blk - blk0 but cost and tour row blk), and the
 smallest batch larger than the configuration's grid of three workgroups per
 CU, where the forward kernel's persistent loop takes a second block.
 
-Which configuration ran: with TILED_CFG set, tspgpu.cpp's pick_sub returns
+Which configuration ran: with TILED_CFG set, k1_launch.cpp's pick_sub returns
 that row or none (the dispatch then falls back to variant 4), so
 last_variant() == 6 means configuration 65; the grid of the large batch
 (three workgroups per CU, not configuration 60's six) says it once more.

@@ -5,7 +5,7 @@ CPU oracle:
 
   A. variant 6 (hk_sub.h): the forward kernel's persistent loop and the
      backtracking kernel's loop (hk_tiled.h) both run at least three times;
-  B. launches split into chunks (tspgpu.cpp ensure_slots; knob K1_CHUNK),
+  B. launches split into chunks (k1_launch.cpp ensure_slots; knob K1_CHUNK),
      the product's 65536-block chunk included;
   C. the `slots` option: the global-table layer kernels reuse three slots
      (and their LDS end layers), the LDS-table kernels loop over a batch of
@@ -161,7 +161,7 @@ def test_forward_and_backtracking_loops_run_three_times(variant, cfg, vb, n):
         got = _solve(ctx, d)
         assert ctx.last_variant() == variant == 6
         assert B_LOOP > 2 * ctx.last_grid()
-        # the backtracking grid (tspgpu.cpp solve_sub): TSPGPU_TILED_BTWG = 6 workgroups
+        # the backtracking grid (k1_launch.cpp solve_sub): TSPGPU_TILED_BTWG = 6 workgroups
         # per CU of kTiledBtWaves = 4 waves, a block per wave (hk_tiled.h)
         assert B_LOOP > 2 * cu * 6 * 4
         _compare(got, ref, src)

@@ -110,7 +110,7 @@ def test_retired_layer_variants_run_variant_2(k1, n):
 @pytest.mark.parametrize("n,vb,expect", [(13, 8, 6), (14, 8, 6), (15, 8, 6), (16, 8, 6), (12, 8, 2), (16, 4, 6),
                                          (15, 4, 2)])
 def test_large_batch_default_per_size(n, vb, expect):
-    """The large-batch default at each size (tspgpu.cpp: the sub-cube kernel
+    """The large-batch default at each size (k1_launch.cpp: the sub-cube kernel
     at 13-16 cities f64 and 16 cities i32, the compact layer pass elsewhere),
     every block against the oracle."""
     d = _blocks(n, B_BIG, 40 + n)

@@ -119,6 +119,7 @@ class DeviceK1:
         self.tour = self._keep(ctx.alloc(4 * B * (n + 1)))
         self.status = self._keep(ctx.alloc(4 * B))
         ctx.solve_cities_device(self.cities, n, B, self.cost, self.tour, self.status, stream)
+        self.k1_stream = stream
 
     def _keep(self, p):
         self.ptrs.append(p)
@@ -145,6 +146,9 @@ class DeviceK1:
         return [(int(c["id"]), float(c["x"]), float(c["y"])) for c in got]
 
     def poke(self, ptr, arr):
+        # (K1 is left running on its stream, and the copy below goes through the
+        # context's: without this wait K1's scatter can overwrite what is poked)
+        self.ctx.synchronize(self.k1_stream)
         arr = np.ascontiguousarray(arr)
         rc = tspgpu.lib().tspgpu_memcpy_htod(self.ctx.handle, ptr, arr.ctypes.data, arr.nbytes)
         assert rc == 0

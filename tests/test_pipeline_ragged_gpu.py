@@ -70,6 +70,7 @@ class RaggedK1:
         self.tour = self._keep(ctx.alloc(4 * self.B * self.stride))
         self.status = self._keep(ctx.alloc(4 * self.B))
         ctx.solve_cities_ragged_device(self.cities, self.ns, self.cost, self.tour, self.stride, self.status, stream)
+        self.k1_stream = stream
 
     _keep = DeviceK1._keep
     path_buffer = DeviceK1.path_buffer

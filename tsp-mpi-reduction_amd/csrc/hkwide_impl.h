@@ -29,6 +29,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -267,13 +268,6 @@ __global__ void wide_close(const V *__restrict__ dist, int N, const WideInfo *__
     }
 }
 
-inline int herr(hipError_t e)
-{
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    return -EIO;
-}
-
 // Device buffers of one table size and value type, kept in the context
 // between calls (tab, dist and cost hold values of type `dtype`).
 // (A hipGraph capture of the N launches was measured: same device time,
@@ -281,24 +275,15 @@ inline int herr(hipError_t e)
 struct WideState {
     int N = 0;
     int dtype = -1;  // TSPGPU_F64 / TSPGPU_I32
-    void *tab = nullptr, *dist = nullptr, *cost = nullptr;
-    int32_t *tour = nullptr;
-    WideInfo *info = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    tspgpu::DevBuf<void> tab, dist, cost;
+    tspgpu::DevBuf<int32_t> tour;
+    tspgpu::DevBuf<WideInfo> info;
+    tspgpu::Event e0, e1;
 };
 
-// (stored in the context as wide_free: either translation unit's copy frees
+// (the context's deleter for wide_cache: either translation unit's copy frees
 // a state of either type)
-inline void wide_state_free(void *p)
-{
-    WideState *w = static_cast<WideState *>(p);
-    if (!w) return;
-    if (w->e0) (void)hipEventDestroy(w->e0);
-    if (w->e1) (void)hipEventDestroy(w->e1);
-    for (void *q : {w->tab, w->dist, w->cost, (void *)w->tour, (void *)w->info})
-        if (q) (void)hipFree(q);
-    delete w;
-}
+inline void wide_state_free(void *p) { delete static_cast<WideState *>(p); }
 
 template <typename V>
 void launch_push(int t, int grid, hipStream_t st, const V *dist, int N, const WideInfo *info, V *tab)
@@ -321,9 +306,9 @@ template <typename V>
 void enqueue_wide(const WideState *w, const WideInfo &h, int n, int cus, hipStream_t st)
 {
     const int N = n - 1;
-    V *tab = static_cast<V *>(w->tab);
-    const V *dist = static_cast<const V *>(w->dist);
-    V *cost = static_cast<V *>(w->cost);
+    V *tab = static_cast<V *>(w->tab.p);
+    const V *dist = static_cast<const V *>(w->dist.p);
+    V *cost = static_cast<V *>(w->cost.p);
     hipLaunchKernelGGL(wide_layer1<V>, dim3(1), dim3(64), 0, st, dist, n, tab);
     // per-destination (pull) form up to 17 cities, where both are bound by the
     // ~8 us kernel boundary per layer and pull is a little faster; the knob
@@ -334,9 +319,9 @@ void enqueue_wide(const WideState *w, const WideInfo &h, int n, int cus, hipStre
             const unsigned long long blocks = (h.cnt[t] + kWideThreads - 1) / kWideThreads;
             const unsigned long long cap = (unsigned long long)cus * 16;
             const int grid = (int)(blocks < cap ? blocks : cap);
-            launch_push<V>(t, grid, st, dist, N, w->info, tab);
+            launch_push<V>(t, grid, st, dist, N, w->info.p, tab);
         }
-        hipLaunchKernelGGL(wide_close<V>, dim3(1), dim3(64), 0, st, dist, N, w->info, tab, cost, w->tour);
+        hipLaunchKernelGGL(wide_close<V>, dim3(1), dim3(64), 0, st, dist, N, w->info.p, tab, cost, w->tour.p);
         return;
     }
     for (int s = 2; s <= N; ++s) {
@@ -344,9 +329,9 @@ void enqueue_wide(const WideState *w, const WideInfo &h, int n, int cus, hipStre
         const unsigned long long blocks = (total + kWideThreads - 1) / kWideThreads;
         const unsigned long long cap = (unsigned long long)cus * 16;
         const int grid = (int)(blocks < cap ? blocks : cap);
-        hipLaunchKernelGGL(wide_layer<V>, dim3(grid), dim3(kWideThreads), 0, st, dist, N, w->info, s, tab);
+        hipLaunchKernelGGL(wide_layer<V>, dim3(grid), dim3(kWideThreads), 0, st, dist, N, w->info.p, s, tab);
     }
-    hipLaunchKernelGGL(wide_close<V>, dim3(1), dim3(64), 0, st, dist, N, w->info, tab, cost, w->tour);
+    hipLaunchKernelGGL(wide_close<V>, dim3(1), dim3(64), 0, st, dist, N, w->info.p, tab, cost, w->tour.p);
 }
 
 // One validated instance (3 <= n <= 31, values checked by the caller) on the
@@ -372,35 +357,29 @@ int solve_wide(tspgpu_ctx *c, const V *dist, int n, V *cost_out, int32_t *tour_o
     std::lock_guard<std::mutex> g(c->mu);
     if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
     hipStream_t st = c->stream;
-    WideState *w = static_cast<WideState *>(c->wide_cache);
+    WideState *w = static_cast<WideState *>(c->wide_cache.get());
+    std::unique_ptr<WideState> mine;  // a state this call owns: too large to keep
     if (!w || w->N != N || w->dtype != WideVal<V>::dtype) {
-        if (w) wide_state_free(w);
-        c->wide_cache = nullptr;
-        c->wide_free = nullptr;
+        c->wide_cache.reset();
         size_t freeb = 0, totalb = 0;
         if (hipMemGetInfo(&freeb, &totalb) == hipSuccess && tab_bytes + (64u << 20) > freeb) return -ENOMEM;
-        w = new (std::nothrow) WideState();
+        mine.reset(w = new (std::nothrow) WideState());
         if (!w) return -ENOMEM;
         w->N = N;
         w->dtype = WideVal<V>::dtype;
-        hipError_t e = hipMalloc(&w->tab, tab_bytes);
-        if (e == hipSuccess) e = hipMalloc(&w->dist, sizeof(V) * n * n);
-        if (e == hipSuccess) e = hipMalloc((void **)&w->info, sizeof(WideInfo));
-        if (e == hipSuccess) e = hipMalloc(&w->cost, sizeof(V));
-        if (e == hipSuccess) e = hipMalloc((void **)&w->tour, sizeof(int32_t) * (n + 1));
-        if (e == hipSuccess) e = xcopy_async(w->info, &h, sizeof h, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventCreate(&w->e0);
-        if (e == hipSuccess) e = hipEventCreate(&w->e1);
+        int rc = tspgpu::dev_reserve(w->tab, tab_bytes);
+        if (!rc) rc = tspgpu::dev_reserve(w->dist, sizeof(V) * n * n);
+        if (!rc) rc = tspgpu::dev_reserve(w->info, sizeof(WideInfo));
+        if (!rc) rc = tspgpu::dev_reserve(w->cost, sizeof(V));
+        if (!rc) rc = tspgpu::dev_reserve(w->tour, sizeof(int32_t) * (n + 1));
+        if (rc) return rc;
+        hipError_t e = xcopy_async(w->info, &h, sizeof h, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventCreate(&w->e0.p);
+        if (e == hipSuccess) e = hipEventCreate(&w->e1.p);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            wide_state_free(w);
-            return herr(e);
-        }
+        if (e != hipSuccess) return tspgpu::hip_err(e);
         // keep small tables for the next call; free >1 GB ones after use
-        if (tab_bytes <= ((size_t)1 << 30)) {
-            c->wide_cache = w;
-            c->wide_free = wide_state_free;
-        }
+        if (tab_bytes <= ((size_t)1 << 30)) c->wide_cache = tspgpu_erased(mine.release(), wide_state_free);
     }
     hipError_t e = xcopy_async(w->dist, dist, sizeof(V) * n * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
@@ -417,8 +396,7 @@ int solve_wide(tspgpu_ctx *c, const V *dist, int n, V *cost_out, int32_t *tour_o
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, w->e0, w->e1) == hipSuccess) *kernel_ms = ms;
     }
-    if (c->wide_cache != w) wide_state_free(w);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return tspgpu::hip_err(e);
     return *cost_out < 0 ? -EIO : 0;
 }
 

@@ -42,6 +42,7 @@
 #include <string>
 #include <vector>
 
+#include "abi_internal.h"
 #include "ctx.h"
 #include "paths.h"
 #include "xfer.h"
@@ -49,6 +50,9 @@
 #include "wave.h"
 #include "tspgpu.h"
 
+using tspgpu::DevBuf;
+using tspgpu::hip_err;
+using tspgpu::Pinned;
 using tspgpu::xcopy_async;
 
 namespace {
@@ -604,36 +608,21 @@ double hswap(const tspgpu_city &A, const tspgpu_city &B, const tspgpu_city &C, c
     return ((hdist(A, D) + hdist(B, C)) - hdist(A, B)) - hdist(C, D);  // tsp.cpp:197-200
 }
 
-int herr(hipError_t e)
-{
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    return -EIO;
-}
-
-struct DVec {
-    tspgpu_city *p = nullptr;
-    size_t len = 0, cap = 0;
-    // grows only when nothing in flight references it (callers reserve up front)
+// a path on the device: the buffer (capacity in cities) and the cities in use
+struct DVec : DevBuf<tspgpu_city> {
+    size_t len = 0;
+    // grows only when nothing in flight references it (callers reserve up
+    // front); the cities in use move to the new buffer
     int reserve(size_t n, hipStream_t st)
     {
         if (n <= cap) return 0;
-        size_t c = std::max<size_t>(n, cap * 2 + 64);
-        tspgpu_city *q = nullptr;
-        hipError_t e = hipMalloc((void **)&q, c * sizeof(tspgpu_city));
-        if (e != hipSuccess) return herr(e);
-        if (len) e = xcopy_async(q, p, len * sizeof(tspgpu_city), hipMemcpyDeviceToDevice, st);
+        DevBuf<tspgpu_city> q;
+        hipError_t e = tspgpu::dev_alloc(q, std::max<size_t>(n, cap * 2 + 64));
+        if (e != hipSuccess) return hip_err(e);
+        if (len) e = xcopy_async(q.p, p, len * sizeof(tspgpu_city), hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = c;
-        return herr(e);
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        len = cap = 0;
+        DevBuf<tspgpu_city>::operator=(std::move(q));
+        return hip_err(e);
     }
 };
 
@@ -650,12 +639,12 @@ struct Merger {
     hipStream_t st = nullptr;
     int cus = 256;
     double eps2 = 0.0;
-    Ctl *ctl = nullptr;
-    Cand *cand = nullptr;
-    Pick *picks = nullptr;
-    unsigned long long *blockmin = nullptr;
-    Ctl *hctl = nullptr;    // pinned mirror
-    Pick *hpicks = nullptr; // pinned mirror
+    DevBuf<Ctl> ctl;
+    DevBuf<Cand> cand;
+    DevBuf<Pick> picks;
+    DevBuf<unsigned long long> blockmin;
+    Pinned<Ctl> hctl;     // mirror of ctl
+    Pinned<Pick> hpicks;  // mirror of picks
     struct Op {
         const tspgpu_city *src;
         tspgpu_city *dst;
@@ -672,28 +661,19 @@ struct Merger {
         st = c->stream;
         cus = c->cu_count;
         eps2 = 2.0 * std::ldexp(4.0 * dmax, -36);
-        hipError_t e = hipMalloc((void **)&ctl, sizeof(Ctl));
-        if (e == hipSuccess) e = hipMalloc((void **)&cand, kCandCap * sizeof(Cand));
-        if (e == hipSuccess) e = hipMalloc((void **)&picks, kBatch * sizeof(Pick));
-        if (e == hipSuccess) e = hipMalloc((void **)&blockmin, kMaxBlocks * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&hctl, sizeof(Ctl), 0);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&hpicks, kBatch * sizeof(Pick), 0);
+        hipError_t e = tspgpu::dev_alloc(ctl, 1);
+        if (e == hipSuccess) e = tspgpu::dev_alloc(cand, kCandCap);
+        if (e == hipSuccess) e = tspgpu::dev_alloc(picks, kBatch);
+        if (e == hipSuccess) e = tspgpu::dev_alloc(blockmin, kMaxBlocks);
+        if (e == hipSuccess) e = tspgpu::pinned_alloc(hctl, 1);
+        if (e == hipSuccess) e = tspgpu::pinned_alloc(hpicks, kBatch);
         if (e == hipSuccess) {
             Ctl z{};
             z.minkey = ~0ull;
             e = xcopy_async(ctl, &z, sizeof z, hipMemcpyHostToDevice, st);
         }
         ops.reserve(kBatch);
-        return herr(e);
-    }
-    ~Merger()
-    {
-        if (ctl) (void)hipFree(ctl);
-        if (cand) (void)hipFree(cand);
-        if (picks) (void)hipFree(picks);
-        if (blockmin) (void)hipFree(blockmin);
-        if (hctl) (void)hipHostFree(hctl);
-        if (hpicks) (void)hipHostFree(hpicks);
+        return hip_err(e);
     }
     int grid_for(unsigned long long work) const
     {
@@ -754,7 +734,7 @@ struct Merger {
         Op o{s1.p, tmp.p, L1, c2, L2, cost1, cost2, fold};
         ops.push_back(o);
         enqueue(o, (int)ops.size() - 1);
-        if (hipPeekAtLastError() != hipSuccess) return herr(hipGetLastError());
+        if (hipPeekAtLastError() != hipSuccess) return hip_err(hipGetLastError());
         std::swap(s1, tmp);
         s1.len = (size_t)L1 + M;
         tmp.len = 0;
@@ -772,7 +752,7 @@ struct Merger {
             std::vector<Cand> hc(nc);
             e = xcopy_async(hc.data(), cand, nc * sizeof(Cand), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return herr(e);
+            if (e != hipSuccess) return hip_err(e);
             std::sort(hc.begin(), hc.end(),
                       [](const Cand &x, const Cand &y) { return x.i != y.i ? x.i < y.i : x.j < y.j; });
             for (const Cand &k : hc) {
@@ -790,7 +770,7 @@ struct Merger {
             if (e == hipSuccess)
                 e = xcopy_async(h2.data(), o.c2, o.L2 * sizeof(tspgpu_city), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return herr(e);
+            if (e != hipSuccess) return hip_err(e);
             for (int i = 0; i < o.L1; ++i)
                 for (int j = 0; j < o.L2; ++j) {
                     const tspgpu_city &a = h1[i], &b = h1[(i + 1) % o.L1], &c = h2[j], &d = h2[(j + 1) % o.L2];
@@ -812,12 +792,12 @@ struct Merger {
         for (;;) {
             hipError_t e = xcopy_async(hctl, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return herr(e);
+            if (e != hipSuccess) return hip_err(e);
             const size_t upto = hctl->stall ? (size_t)hctl->stall_at : ops.size();
             if (upto > first) {
                 e = xcopy_async(hpicks + first, picks + first, (upto - first) * sizeof(Pick), hipMemcpyDeviceToHost, st);
                 if (e == hipSuccess) e = hipStreamSynchronize(st);
-                if (e != hipSuccess) return herr(e);
+                if (e != hipSuccess) return hip_err(e);
                 for (size_t m = first; m < upto; ++m) {
                     const Cand &k = hpicks[m].c;
                     *ops[m].target = (*ops[m].target + *ops[m].cost2) + hswap(k.a, k.b, k.c, k.d);
@@ -837,7 +817,7 @@ struct Merger {
             Ctl reset = *hctl;
             reset.fw[0] = reset.fw[1] = ~0ull;
             e = xcopy_async(ctl, &reset, sizeof reset, hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) return herr(e);
+            if (e != hipSuccess) return hip_err(e);
             hipLaunchKernelGGL(find_kernel, dim3(grid_for((unsigned long long)std::max(o.L1, M))),
                                dim3(kMergeThreads), 0, st, o.src, o.L1, o.c2, M, ctl, cand, picks, (int)first,
                                pk.a.id, pk.b.id, pk.c.id, 1);
@@ -845,13 +825,13 @@ struct Merger {
                                dim3(kMergeThreads), 0, st, o.src, o.L1, o.c2, M, ctl, o.dst, (int)first, 1);
             e = xcopy_async(hctl, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return herr(e);
+            if (e != hipSuccess) return hip_err(e);
             if (hctl->stall == 2) return -EDEADLK;
             if (hctl->stall) return -EIO;
             *o.target = (*o.target + *o.cost2) + best;
             ++first;
             for (size_t m = first; m < ops.size(); ++m) enqueue(ops[m], (int)m);
-            if (hipPeekAtLastError() != hipSuccess) return herr(hipGetLastError());
+            if (hipPeekAtLastError() != hipSuccess) return hip_err(hipGetLastError());
         }
         ops.clear();
         return 0;
@@ -934,21 +914,13 @@ int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std:
     for (int c : cnt) nb += c;
     const size_t ncity = bs.total;
     const tspgpu_city *blocks = bs.p;
-    FoldJob *djobs = nullptr;
-    FoldOut *douts = nullptr;
-    Pick *dpicks = nullptr;
-    hipError_t e = hipMalloc((void **)&djobs, P * sizeof(FoldJob));
-    if (e == hipSuccess) e = hipMalloc((void **)&douts, P * sizeof(FoldOut));
-    if (e == hipSuccess) e = hipMalloc((void **)&dpicks, (size_t)std::max(nb, 1) * sizeof(Pick));
-    auto release = [&] {
-        if (djobs) (void)hipFree(djobs);
-        if (douts) (void)hipFree(douts);
-        if (dpicks) (void)hipFree(dpicks);
-    };
-    if (e != hipSuccess) {
-        release();
-        return herr(e);
-    }
+    DevBuf<FoldJob> djobs;
+    DevBuf<FoldOut> douts;
+    DevBuf<Pick> dpicks;
+    hipError_t e = tspgpu::dev_alloc(djobs, P);
+    if (e == hipSuccess) e = tspgpu::dev_alloc(douts, P);
+    if (e == hipSuccess) e = tspgpu::dev_alloc(dpicks, (size_t)std::max(nb, 1));
+    if (e != hipSuccess) return hip_err(e);
     std::vector<FoldJob> jobs(P);
     std::vector<int> firstb(P), cap_at(P, -1);
     std::vector<Pick> hpick((size_t)nb);
@@ -976,7 +948,7 @@ int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std:
         if (e == hipSuccess) e = xcopy_async(outs.data(), douts, aj.size() * sizeof(FoldOut), hipMemcpyDeviceToHost, m.st);
         if (e == hipSuccess) e = hipStreamSynchronize(m.st);
         if (e != hipSuccess) {
-            rc = herr(e);
+            rc = hip_err(e);
             break;
         }
         std::vector<int> again;
@@ -997,7 +969,7 @@ int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std:
                 e = xcopy_async(blk.data(), bs.at(sb), (size_t)Lb * sizeof(tspgpu_city), hipMemcpyDeviceToHost, m.st);
             if (e == hipSuccess) e = hipStreamSynchronize(m.st);
             if (e != hipSuccess) {
-                rc = herr(e);
+                rc = hip_err(e);
                 break;
             }
             Cand pk{};
@@ -1007,7 +979,7 @@ int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std:
             host_picked[(size_t)firstb[r] + o.at] = 1;
             e = xcopy_async(rank[r].p, path.data(), path.size() * sizeof(tspgpu_city), hipMemcpyHostToDevice, m.st);
             if (e != hipSuccess) {
-                rc = herr(e);
+                rc = hip_err(e);
                 break;
             }
             rank[r].len = path.size();
@@ -1022,7 +994,7 @@ int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std:
         std::vector<Pick> dp((size_t)nb);
         e = xcopy_async(dp.data(), dpicks, dp.size() * sizeof(Pick), hipMemcpyDeviceToHost, m.st);
         if (e == hipSuccess) e = hipStreamSynchronize(m.st);
-        rc = herr(e);
+        rc = hip_err(e);
         for (int r = 0; r < P && !rc; ++r) {
             const int b0 = firstb[r];
             rcost[r] = costs[b0];
@@ -1039,9 +1011,8 @@ int persist_folds(Merger &m, const BlockSet &bs, const double *costs, const std:
                 rc = m.merge(rank[r], tmp, &rcost[r], bs.at(firstb[r] + 1 + k), bs.len(firstb[r] + 1 + k),
                              &costs[firstb[r] + 1 + k], true);
     }
-    if (!rc) rc = m.sync();  // (the picks buffer is freed below: nothing in flight may use it)
+    if (!rc) rc = m.sync();  // (the picks buffer is freed on return: nothing in flight may use it)
     (void)hipStreamSynchronize(m.st);
-    release();
     return rc;
 }
 
@@ -1116,7 +1087,7 @@ int reduce_core(tspgpu_ctx *ctx, const BlockSet &bs, const double *costs, int np
     for (int r = 0; r < nprocs && !rc && next < nblocks; ++r) {
         rc = rank[r].reserve(ncity, m.st);
         if (rc) break;
-        rc = herr(xcopy_async(rank[r].p, bs.at(next), (size_t)bs.len(next) * sizeof(tspgpu_city),
+        rc = hip_err(xcopy_async(rank[r].p, bs.at(next), (size_t)bs.len(next) * sizeof(tspgpu_city),
                               hipMemcpyDeviceToDevice, m.st));
         rank[r].len = (size_t)bs.len(next);
         rcost[r] = costs[next];
@@ -1137,7 +1108,7 @@ int reduce_core(tspgpu_ctx *ctx, const BlockSet &bs, const double *costs, int np
         const size_t add = rank[from].len;
         r2 = acc.reserve(std::max(acc.len + add, ncity), m.st);
         if (r2) return r2;
-        r2 = herr(xcopy_async(acc.p + acc.len, rank[from].p, add * sizeof(tspgpu_city), hipMemcpyDeviceToDevice,
+        r2 = hip_err(xcopy_async(acc.p + acc.len, rank[from].p, add * sizeof(tspgpu_city), hipMemcpyDeviceToDevice,
                                  m.st));
         if (r2) return r2;
         acc.len += add;
@@ -1159,14 +1130,11 @@ int reduce_core(tspgpu_ctx *ctx, const BlockSet &bs, const double *costs, int np
         *dest->len = (int)rank[0].len;
         const size_t k = std::min(rank[0].len, (size_t)dest->cap);
         if (k)
-            rc = herr(xcopy_async(dest->p, rank[0].p, k * sizeof(tspgpu_city),
+            rc = hip_err(xcopy_async(dest->p, rank[0].p, k * sizeof(tspgpu_city),
                                   dest->device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, m.st));
     }
     const hipError_t es = hipStreamSynchronize(m.st);
-    if (!rc && dest) rc = herr(es);
-    for (auto &v : rank) v.release();
-    for (auto &v : received) v.release();
-    tmp.release();
+    if (!rc && dest) rc = hip_err(es);
     if (rc) return rc;
     *final_cost = rcost[0];
     return 0;
@@ -1205,20 +1173,12 @@ bool host_fold_ok(const tspgpu_city *paths, int L, const int32_t *len, int nbloc
 // dist and n are the caller's) on the host and, uploaded on st, on the device.
 struct DescTable {
     std::vector<tspgpu::BlockDesc> h;
-    tspgpu::BlockDesc *d = nullptr;
-    ~DescTable()
-    {
-        if (d) (void)hipFree(d);
-    }
+    DevBuf<tspgpu::BlockDesc> d;
     int upload(hipStream_t st)
     {
-        hipError_t e = hipMalloc((void **)&d, h.size() * sizeof(tspgpu::BlockDesc));
-        if (e != hipSuccess) {
-            d = nullptr;
-            return herr(e);
-        }
+        if (hipError_t e = tspgpu::dev_alloc(d, h.size()); e != hipSuccess) return hip_err(e);
         // (an H2D copy has read the host table when it returns: xfer.h)
-        return herr(xcopy_async(d, h.data(), h.size() * sizeof(tspgpu::BlockDesc), hipMemcpyHostToDevice, st));
+        return hip_err(xcopy_async(d, h.data(), h.size() * sizeof(tspgpu::BlockDesc), hipMemcpyHostToDevice, st));
     }
     BlockSet blocks(const tspgpu_city *p) const
     {
@@ -1275,28 +1235,18 @@ int reduce_host(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const int32_t 
     const double dmax = bbox_diagonal(paths, ncity);
     DVec blocks;
     int rc = blocks.reserve(ncity, ctx->stream);
-    if (!rc) rc = herr(xcopy_async(blocks.p, paths, ncity * sizeof(tspgpu_city), hipMemcpyHostToDevice, ctx->stream));
-    if (!rc) rc = herr(hipStreamSynchronize(ctx->stream));
+    if (!rc) rc = hip_err(xcopy_async(blocks.p, paths, ncity * sizeof(tspgpu_city), hipMemcpyHostToDevice, ctx->stream));
+    if (!rc) rc = hip_err(hipStreamSynchronize(ctx->stream));
     blocks.len = ncity;
     if (!rc && len) rc = table.upload(ctx->stream);
     std::string text;
     if (!rc)
         rc = reduce_core(ctx, len ? table.blocks(blocks.p) : uniform_blocks(blocks.p, L, nblocks), costs, nprocs, dmax,
                          host_fold_ok(paths, L, len, nblocks), final_cost, text, dest);
-    blocks.release();
     if (rc) return rc;
     put_log(text, log, logcap);
     return dest && *dest->len > dest->cap ? -ENOSPC : 0;
 }
-
-// a hipEvent_t that lives for one call
-struct EventPair {
-    hipEvent_t a = nullptr;
-    ~EventPair()
-    {
-        if (a) (void)hipEventDestroy(a);
-    }
-};
 
 }  // namespace
 
@@ -1320,20 +1270,16 @@ int tspgpu_merge(tspgpu_ctx *ctx, const tspgpu_city *p1, int L1, double c1, cons
     hipError_t e = hipSuccess;
     if (!rc) e = xcopy_async(s.p, p1, L1 * sizeof(tspgpu_city), hipMemcpyHostToDevice, m.st);
     if (!rc && e == hipSuccess) e = xcopy_async(b.p, p2, L2 * sizeof(tspgpu_city), hipMemcpyHostToDevice, m.st);
-    if (!rc) rc = herr(e);
+    if (!rc) rc = hip_err(e);
     s.len = L1;
     double cost = c1;
     if (!rc) rc = m.merge(s, t, &cost, b.p, L2, &c2);
     if (!rc) rc = m.sync();
-    if (!rc) rc = herr(xcopy_async(out, s.p, s.len * sizeof(tspgpu_city), hipMemcpyDeviceToHost, m.st));
-    if (!rc) rc = herr(hipStreamSynchronize(m.st));
-    const int len = (int)s.len;
-    s.release();
-    t.release();
-    b.release();
+    if (!rc) rc = hip_err(xcopy_async(out, s.p, s.len * sizeof(tspgpu_city), hipMemcpyDeviceToHost, m.st));
+    if (!rc) rc = hip_err(hipStreamSynchronize(m.st));
     if (rc) return rc;
     *cost_out = cost;
-    return len;
+    return (int)s.len;
 }
 
 int tspgpu_reduce(tspgpu_ctx *ctx, const tspgpu_city *paths, int L, const double *costs, int nblocks, int nprocs,
@@ -1412,56 +1358,50 @@ int reduce_device_front(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int3
     std::lock_guard<std::mutex> g(ctx->mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return -ENODEV;
     hipStream_t st = ctx->stream, caller = (hipStream_t)hip_stream;
-    EventPair order;
+    tspgpu::Event order;
     hipError_t e = hipSuccess;
     if (caller != st) {
         // K1's outputs were produced on the caller's stream
-        e = hipEventCreateWithFlags(&order.a, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(order.a, caller);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, order.a, 0);
-        if (e != hipSuccess) return herr(e);
+        e = hipEventCreateWithFlags(&order.p, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(order, caller);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, order, 0);
+        if (e != hipSuccess) return hip_err(e);
     }
     // per call: the gathered paths, the facts, the id bitmap
     DVec blocks;
-    PathFacts *d_facts = nullptr;
-    uint32_t *d_bitmap = nullptr;
+    DevBuf<PathFacts> d_facts;
+    DevBuf<uint32_t> d_bitmap;
     // (whole words; for nblocks paths of L cities this is path_bitmap_bytes(nblocks, L))
     const size_t bitmap_bytes = (size_t)tspgpu::path_bitmap_bytes_total(ncity);
-    auto release = [&] {
-        blocks.release();
-        if (d_facts) (void)hipFree(d_facts);
-        if (d_bitmap) (void)hipFree(d_bitmap);
-    };
     int rc = blocks.reserve(ncity, st);
-    if (!rc) rc = herr(hipMalloc((void **)&d_facts, sizeof(PathFacts)));
-    if (!rc && min_len >= 3) rc = herr(hipMalloc((void **)&d_bitmap, bitmap_bytes));
+    if (!rc) rc = tspgpu::dev_reserve(d_facts, sizeof(PathFacts));
+    if (!rc && min_len >= 3) rc = tspgpu::dev_reserve(d_bitmap, bitmap_bytes);
     if (!rc && ns) rc = table.upload(st);
     // (the timing events are the context's, created on the first call)
-    if (!rc && !ctx->ev_k3_gather[0]) rc = herr(hipEventCreate(&ctx->ev_k3_gather[0]));
-    if (!rc && !ctx->ev_k3_gather[1]) rc = herr(hipEventCreate(&ctx->ev_k3_gather[1]));
+    if (!rc && !ctx->ev_k3_gather[0]) rc = hip_err(hipEventCreate(&ctx->ev_k3_gather[0].p));
+    if (!rc && !ctx->ev_k3_gather[1]) rc = hip_err(hipEventCreate(&ctx->ev_k3_gather[1].p));
     PathFacts facts = tspgpu::path_facts_init();
     std::vector<double> costs((size_t)nblocks);
     const int grid_cap = ctx->cu_count * 8;
-    if (!rc) rc = herr(xcopy_async(d_facts, &facts, sizeof facts, hipMemcpyHostToDevice, st));
-    if (!rc && d_bitmap) rc = herr(hipMemsetAsync(d_bitmap, 0, bitmap_bytes, st));
-    if (!rc) rc = herr(hipEventRecord(ctx->ev_k3_gather[0], st));
+    if (!rc) rc = hip_err(xcopy_async(d_facts, &facts, sizeof facts, hipMemcpyHostToDevice, st));
+    if (!rc && d_bitmap) rc = hip_err(hipMemsetAsync(d_bitmap, 0, bitmap_bytes, st));
+    if (!rc) rc = hip_err(hipEventRecord(ctx->ev_k3_gather[0], st));
     if (!rc)
-        rc = herr(ns ? tspgpu::launch_paths_gather_ragged(d_cities, d_tour, tour_stride, d_status, table.d, nblocks,
+        rc = hip_err(ns ? tspgpu::launch_paths_gather_ragged(d_cities, d_tour, tour_stride, d_status, table.d, nblocks,
                                                           blocks.p, d_facts, grid_cap, st)
                      : tspgpu::launch_paths_gather(d_cities, d_tour, d_status, n, nblocks, blocks.p, d_facts, grid_cap,
                                                    st));
     if (!rc && d_bitmap)
-        rc = herr(ns ? tspgpu::launch_paths_unique_ragged(blocks.p, table.d, nblocks, ncity, d_bitmap, d_facts,
+        rc = hip_err(ns ? tspgpu::launch_paths_unique_ragged(blocks.p, table.d, nblocks, ncity, d_bitmap, d_facts,
                                                           grid_cap, st)
                      : tspgpu::launch_paths_unique(blocks.p, L, nblocks, d_bitmap, d_facts, grid_cap, st));
-    if (!rc) rc = herr(hipEventRecord(ctx->ev_k3_gather[1], st));
+    if (!rc) rc = hip_err(hipEventRecord(ctx->ev_k3_gather[1], st));
     // (the D2H copies are complete when they return: xfer.h)
-    if (!rc) rc = herr(xcopy_async(&facts, d_facts, sizeof facts, hipMemcpyDeviceToHost, st));
-    if (!rc) rc = herr(xcopy_async(costs.data(), d_cost, costs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (!rc) rc = herr(hipStreamSynchronize(st));
+    if (!rc) rc = hip_err(xcopy_async(&facts, d_facts, sizeof facts, hipMemcpyDeviceToHost, st));
+    if (!rc) rc = hip_err(xcopy_async(costs.data(), d_cost, costs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!rc) rc = hip_err(hipStreamSynchronize(st));
     if (rc) {
         (void)hipStreamSynchronize(st);
-        release();
         return rc;
     }
     blocks.len = ncity;
@@ -1473,8 +1413,8 @@ int reduce_device_front(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int3
         *final_cost = costs[0];
         *path_len = L;
         const size_t k = (size_t)std::min(L, path_cap);
-        if (k) rc = herr(xcopy_async(d_path_out, blocks.p, k * sizeof(tspgpu_city), hipMemcpyDeviceToDevice, st));
-        if (!rc) rc = herr(hipStreamSynchronize(st));
+        if (k) rc = hip_err(xcopy_async(d_path_out, blocks.p, k * sizeof(tspgpu_city), hipMemcpyDeviceToDevice, st));
+        if (!rc) rc = hip_err(hipStreamSynchronize(st));
     } else if (!rc) {
         // the host's own formula over the device's exact extrema: the bits of bbox_diagonal
         const double dmax = tspgpu::path_facts_diagonal(facts);
@@ -1483,7 +1423,6 @@ int reduce_device_front(tspgpu_ctx *ctx, const tspgpu_city *d_cities, const int3
         rc = reduce_core(ctx, ns ? table.blocks(blocks.p) : uniform_blocks(blocks.p, L, nblocks), costs.data(), nprocs,
                          dmax, fold_ok, final_cost, text, &dest);
     }
-    release();
     if (rc) return rc;
     put_log(text, log, logcap);
     return *path_len > path_cap ? -ENOSPC : 0;
@@ -1523,92 +1462,74 @@ int tspgpu_reduce_device_last_ms(const tspgpu_ctx *ctx, double *gather_ms)
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// tspgpu_pipeline_cities (ns null: n cities in every block) and
+// tspgpu_pipeline_cities_ragged (ns: packed blocks of ns[b] cities).  Per
+// call: the cities, K1's outputs (tour rows of max n + 1 entries) and the
+// merged tour on the device.  (Each step takes the context's mutex itself;
+// the buffers are this call's.)
+int pipeline_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, const int32_t *ns, bool ragged, int nblocks,
+                    int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log,
+                    int logcap)
+{
+    if (log && logcap > 0) log[0] = 0;
+    if (!final_cost || !path_len || nblocks < 1 || nprocs < 1 || nblocks < nprocs) return -EINVAL;
+    if (path_cap < 0 || (!path_out && path_cap > 0)) return -EINVAL;
+    int max_n = 0;
+    int64_t ncities = 0;
+    if (tspgpu::cities_args(ctx, cities, n, ns, ragged, nblocks, 2, &max_n, &ncities)) return -EINVAL;
+    const int stride = max_n + 1;
+    // (every step below sets the same device, so it is still current when the
+    // buffers free themselves on return)
+    if (hipSetDevice(ctx->device) != hipSuccess) return -ENODEV;
+    DevBuf<tspgpu_city> d_cities, d_path;
+    DevBuf<double> d_cost;
+    DevBuf<int32_t> d_tour, d_status;
+    const size_t ib = (size_t)ncities * sizeof(tspgpu_city);
+    int rc = tspgpu::dev_reserve(d_cities, ib);
+    if (!rc) rc = tspgpu::dev_reserve(d_cost, (size_t)nblocks * sizeof(double));
+    if (!rc) rc = tspgpu::dev_reserve(d_tour, (size_t)nblocks * stride * sizeof(int32_t));
+    if (!rc) rc = tspgpu::dev_reserve(d_status, (size_t)nblocks * sizeof(int32_t));
+    if (!rc && path_cap > 0) rc = tspgpu::dev_reserve(d_path, (size_t)path_cap * sizeof(tspgpu_city));
+    void *st = tspgpu_stream(ctx);
+    if (!rc) rc = tspgpu_memcpy_htod(ctx, d_cities, cities, ib);
+    if (!rc)
+        rc = ragged ? tspgpu_solve_cities_ragged_device(ctx, d_cities, ns, nblocks, d_cost, d_tour, stride, d_status, st)
+                    : tspgpu_solve_cities_device(ctx, d_cities, n, nblocks, d_cost, d_tour, d_status, st);
+    if (rc) {
+        (void)tspgpu_stream_synchronize(ctx, st);
+        return rc;
+    }
+    const int red = reduce_device_front(ctx, d_cities, d_tour, stride, d_cost, d_status, n, ns, nblocks, nprocs,
+                                        final_cost, d_path, path_cap, path_len, log, logcap, st);
+    if (red == 0 || red == -ENOSPC) {
+        const size_t k = (size_t)std::min(*path_len, path_cap);
+        if (k) rc = tspgpu_memcpy_dtoh(ctx, path_out, d_path, k * sizeof(tspgpu_city));
+    }
+    return rc ? rc : red;
+}
+
+}  // namespace
+
+extern "C" {
+
 int tspgpu_pipeline_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int n, int nblocks, int nprocs,
                            double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len, char *log,
                            int logcap)
 {
-    if (log && logcap > 0) log[0] = 0;
-    if (!ctx || !cities || !final_cost || !path_len) return -EINVAL;
-    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs || n < 2 || n > TSPGPU_MAX_CITIES) return -EINVAL;
-    if (path_cap < 0 || (!path_out && path_cap > 0)) return -EINVAL;
-    // per call: the cities, K1's outputs and the merged tour on the device.
-    // (each step takes the context's mutex itself; the buffers are this call's)
-    const size_t ib = (size_t)nblocks * n * sizeof(tspgpu_city);
-    const size_t tb = (size_t)nblocks * (n + 1) * sizeof(int32_t);
-    void *d_cities = nullptr, *d_cost = nullptr, *d_tour = nullptr, *d_status = nullptr, *d_path = nullptr;
-    int rc = tspgpu_device_alloc(ctx, ib, &d_cities);
-    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(double), &d_cost);
-    if (!rc) rc = tspgpu_device_alloc(ctx, tb, &d_tour);
-    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(int32_t), &d_status);
-    if (!rc && path_cap > 0) rc = tspgpu_device_alloc(ctx, (size_t)path_cap * sizeof(tspgpu_city), &d_path);
-    void *st = tspgpu_stream(ctx);
-    if (!rc) rc = tspgpu_memcpy_htod(ctx, d_cities, cities, ib);
-    if (!rc)
-        rc = tspgpu_solve_cities_device(ctx, (const tspgpu_city *)d_cities, n, nblocks, (double *)d_cost,
-                                        (int32_t *)d_tour, (int32_t *)d_status, st);
-    int red = 0;
-    if (!rc) {
-        red = tspgpu_reduce_device(ctx, (const tspgpu_city *)d_cities, (const int32_t *)d_tour, (const double *)d_cost,
-                                   (const int32_t *)d_status, n, nblocks, nprocs, final_cost, (tspgpu_city *)d_path,
-                                   path_cap, path_len, log, logcap, st);
-        if (red == 0 || red == -ENOSPC) {
-            const size_t k = (size_t)std::min(*path_len, path_cap);
-            if (k) rc = tspgpu_memcpy_dtoh(ctx, path_out, d_path, k * sizeof(tspgpu_city));
-        }
-    } else {
-        (void)tspgpu_stream_synchronize(ctx, st);
-    }
-    for (void *p : {d_cities, d_cost, d_tour, d_status, d_path})
-        if (p) (void)tspgpu_device_free(ctx, p);
-    return rc ? rc : red;
+    return pipeline_cities(ctx, cities, n, nullptr, false, nblocks, nprocs, final_cost, path_out, path_cap, path_len,
+                           log, logcap);
 }
 
 int tspgpu_pipeline_cities_ragged(tspgpu_ctx *ctx, const tspgpu_city *cities, const int32_t *n, int nblocks,
                                   int nprocs, double *final_cost, tspgpu_city *path_out, int path_cap, int *path_len,
                                   char *log, int logcap)
 {
-    if (log && logcap > 0) log[0] = 0;
-    if (!ctx || !cities || !n || !final_cost || !path_len) return -EINVAL;
-    if (nblocks < 1 || nprocs < 1 || nblocks < nprocs) return -EINVAL;
-    if (path_cap < 0 || (!path_out && path_cap > 0)) return -EINVAL;
-    size_t ncities = 0;
-    int max_n = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        if (n[b] < 2 || n[b] > TSPGPU_MAX_CITIES) return -EINVAL;
-        ncities += (size_t)n[b];
-        max_n = std::max(max_n, (int)n[b]);
-    }
-    // per call, as tspgpu_pipeline_cities: the packed cities, K1's outputs
-    // (tour rows of max n + 1 entries) and the merged tour on the device
-    const int stride = max_n + 1;
-    const size_t ib = ncities * sizeof(tspgpu_city);
-    const size_t tb = (size_t)nblocks * stride * sizeof(int32_t);
-    void *d_cities = nullptr, *d_cost = nullptr, *d_tour = nullptr, *d_status = nullptr, *d_path = nullptr;
-    int rc = tspgpu_device_alloc(ctx, ib, &d_cities);
-    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(double), &d_cost);
-    if (!rc) rc = tspgpu_device_alloc(ctx, tb, &d_tour);
-    if (!rc) rc = tspgpu_device_alloc(ctx, (size_t)nblocks * sizeof(int32_t), &d_status);
-    if (!rc && path_cap > 0) rc = tspgpu_device_alloc(ctx, (size_t)path_cap * sizeof(tspgpu_city), &d_path);
-    void *st = tspgpu_stream(ctx);
-    if (!rc) rc = tspgpu_memcpy_htod(ctx, d_cities, cities, ib);
-    if (!rc)
-        rc = tspgpu_solve_cities_ragged_device(ctx, (const tspgpu_city *)d_cities, n, nblocks, (double *)d_cost,
-                                               (int32_t *)d_tour, stride, (int32_t *)d_status, st);
-    int red = 0;
-    if (!rc) {
-        red = tspgpu_reduce_ragged_device(ctx, (const tspgpu_city *)d_cities, n, (const int32_t *)d_tour, stride,
-                                          (const double *)d_cost, (const int32_t *)d_status, nblocks, nprocs,
-                                          final_cost, (tspgpu_city *)d_path, path_cap, path_len, log, logcap, st);
-        if (red == 0 || red == -ENOSPC) {
-            const size_t k = (size_t)std::min(*path_len, path_cap);
-            if (k) rc = tspgpu_memcpy_dtoh(ctx, path_out, d_path, k * sizeof(tspgpu_city));
-        }
-    } else {
-        (void)tspgpu_stream_synchronize(ctx, st);
-    }
-    for (void *p : {d_cities, d_cost, d_tour, d_status, d_path})
-        if (p) (void)tspgpu_device_free(ctx, p);
-    return rc ? rc : red;
+    return pipeline_cities(ctx, cities, 0, n, true, nblocks, nprocs, final_cost, path_out, path_cap, path_len, log,
+                           logcap);
 }
 
 }  // extern "C"

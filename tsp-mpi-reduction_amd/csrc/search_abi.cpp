@@ -54,61 +54,6 @@ constexpr size_t kStageSpec = 24 * 1024;  // h_stage: tables below, speculative 
 constexpr unsigned kSpecRecs = 512;
 constexpr size_t kStageBytes = kStageSpec + 8 * kFetchWords + sizeof(SearchRecord) * kSpecRecs;
 
-namespace {
-
-// Move-only owner of one HIP handle and its capacity (in the owner's unit):
-// a move leaves the source null with capacity 0, the destructor frees.  Frees
-// need the search's device current: tspgpu_search_destroy and the context's
-// release set it before they drop a SearchBuffers.
-template <typename P, auto Free>
-struct Owned {
-    P p = nullptr;
-    size_t cap = 0;
-    Owned() = default;
-    Owned(Owned &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
-    Owned &operator=(Owned &&o) noexcept
-    {
-        if (this != &o) {
-            reset();
-            p = o.p, cap = o.cap;
-            o.p = nullptr, o.cap = 0;
-        }
-        return *this;
-    }
-    ~Owned() { reset(); }
-    void reset()
-    {
-        if (p) (void)Free(p);
-        p = nullptr, cap = 0;
-    }
-    operator P() const { return p; }
-};
-template <typename T>
-using DevBuf = Owned<T *, hipFree>;
-template <typename T>
-using Pinned = Owned<T *, hipHostFree>;
-using Event = Owned<hipEvent_t, hipEventDestroy>;
-
-// (re)allocate b for `count` elements
-template <typename T>
-hipError_t dev_alloc(DevBuf<T> &b, size_t count)
-{
-    b.reset();
-    hipError_t e = hipMalloc((void **)&b.p, count * sizeof(T));
-    if (e == hipSuccess) b.cap = count;
-    return e;
-}
-template <typename T>
-hipError_t pinned_alloc(Pinned<T> &b, size_t count)
-{
-    b.reset();
-    hipError_t e = hipHostMalloc((void **)&b.p, count * sizeof(T), hipHostMallocDefault);
-    if (e == hipSuccess) b.cap = count;
-    return e;
-}
-
-}  // namespace
-
 // Every device buffer, pinned host buffer and event of a search — the ONE list
 // of them.  A context keeps the set of its last search between searches
 // (hipMalloc of the tail and frontier buffers costs more than a 16-city search
@@ -220,42 +165,25 @@ namespace {
 
 using tspgpu::host::falling;
 
-int herr(hipError_t e)
-{
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorOutOfMemory) return -ENOMEM;
-    return -EIO;
-}
-
 void pool_free(void *p) { delete static_cast<SearchBuffers *>(p); }
 
 void take_pool(tspgpu_search *s)
 {
-    SearchBuffers *pool = nullptr;
+    tspgpu_erased pool{nullptr, nullptr};
     {
         std::lock_guard<std::mutex> g(s->ctx->mu);
-        pool = static_cast<SearchBuffers *>(s->ctx->search_pool);
-        s->ctx->search_pool = nullptr;
+        pool = std::move(s->ctx->search_pool);
     }
-    if (!pool) return;
-    static_cast<SearchBuffers &>(*s) = std::move(*pool);
-    delete pool;
+    if (pool) static_cast<SearchBuffers &>(*s) = std::move(*static_cast<SearchBuffers *>(pool.get()));
 }
 
 void give_pool(tspgpu_search *s)
 {
     if (!s->d_words) return;  // a failed create: nothing worth keeping
-    auto *pool = new (std::nothrow) SearchBuffers(std::move(static_cast<SearchBuffers &>(*s)));
-    if (!pool) return;
-    {
-        std::lock_guard<std::mutex> g(s->ctx->mu);
-        if (!s->ctx->search_pool) {
-            s->ctx->search_pool = pool;
-            s->ctx->search_pool_free = pool_free;
-            pool = nullptr;
-        }
-    }
-    delete pool;  // the context has one already: free ours
+    tspgpu_erased pool(new (std::nothrow) SearchBuffers(std::move(static_cast<SearchBuffers &>(*s))), pool_free);
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    if (pool && !s->ctx->search_pool) s->ctx->search_pool = std::move(pool);
+    // (the context has one already: ours is freed here)
 }
 }  // namespace
 
@@ -477,7 +405,7 @@ static int search_create(tspgpu_ctx *c, const void *dist, int dtype, int n, int 
     if (e == hipSuccess) e = create_events(s);
     if (e != hipSuccess) {
         tspgpu_search_destroy(s);
-        return herr(e);
+        return hip_err(e);
     }
     *out = s;
     return 0;
@@ -589,7 +517,7 @@ int tspgpu_search_set_bound(tspgpu_search *s, double bound)
     if (e == hipSuccess)  // word 14: a chain's starting incumbent (read by its overflow rerun)
         e = hipMemcpyAsync(s->d_words + 14, &w, 8, hipMemcpyHostToDevice, s->ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
-    return herr(e);
+    return hip_err(e);
 }
 
 static SearchArgs args_of(tspgpu_search *s)
@@ -660,7 +588,7 @@ static int ensure_items(tspgpu_search *s, int which, size_t count)
     // grow geometrically (up to 2^27 items) so that rounds rarely reallocate
     const size_t cap = std::max<size_t>(std::max<size_t>(count, 1024),
                                         std::min<size_t>(2 * s->d_items[which].cap, (size_t)1 << 27));
-    return herr(dev_alloc(s->d_items[which], cap));
+    return hip_err(dev_alloc(s->d_items[which], cap));
 }
 
 // the statistics lines, summed: [0] nodes, [1] lane slots, [2] active lane steps, [3] item loads
@@ -678,7 +606,7 @@ static int read_words_stats(tspgpu_search *s, unsigned long long (&w)[5], uint64
     hipError_t e = hipMemcpyAsync(h, s->d_stats, kStatBytes, hipMemcpyDeviceToHost, s->ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(hw, s->d_words, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     for (int i = 0; i < 4; ++i) {
         out[i] = 0;
         for (int l = 0; l < kStatLines; ++l) out[i] += h[l * kStatStride + i];
@@ -705,7 +633,7 @@ static int front_spare(tspgpu_search *s, size_t count, int *rc)
     const size_t cap = std::max<size_t>(4096, count <= 4096 ? 4096 : (count + gran - 1) / gran * gran);
     DevBuf<PathItem> b;
     if (hipError_t e = dev_alloc(b, cap); e != hipSuccess) {
-        *rc = herr(e);
+        *rc = hip_err(e);
         return -1;
     }
     s->fb.push_back(std::move(b));
@@ -739,19 +667,19 @@ static int launch_and_count(tspgpu_search *s, bool seed, int grid, SearchArgs &a
 {
     hipStream_t st = s->ctx->stream;
     hipError_t e = zero_queue(s);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     if (sync) (void)hipEventRecord(s->e0, st);  // (a chain times itself: SearchArgs::t_start)
     if (seed && suffix_sets)  // the frontier's seeds and its suffix table, side by side in one launch
         e = launch_prologue(a, s->dtype == TSPGPU_F64, grid, suffix_sets);
     else
         e = seed ? launch_seed(a, s->dtype == TSPGPU_F64, grid) : launch_round(a, s->dtype == TSPGPU_F64, grid);
     if (sync) (void)hipEventRecord(s->e1, st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     if (!sync) return 0;
     unsigned long long out = 0;
     e = hipMemcpyAsync(&out, s->d_words + 4, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
     s->pending = (uint32_t)out;
@@ -773,16 +701,16 @@ static int build_suffix(tspgpu_search *s, bool launch, uint32_t *sets_out)
     const uint32_t sets = search_binom(N, L), off = sets * (uint32_t)L;
     hipStream_t st = s->ctx->stream;
     if (s->d_hsuf.cap < off)
-        if (hipError_t e = dev_alloc(s->d_hsuf, off); e != hipSuccess) return herr(e);
+        if (hipError_t e = dev_alloc(s->d_hsuf, off); e != hipSuccess) return hip_err(e);
     s->hs_len = L;
     *sets_out = sets;
     if (!launch) return 0;  // the caller launches it (with the seeds)
     SearchArgs a = args_of(s);
     (void)hipEventRecord(s->e0, st);
-    if (hipError_t e = launch_suffix(a, s->dtype == TSPGPU_F64, sets); e != hipSuccess) return herr(e);
+    if (hipError_t e = launch_suffix(a, s->dtype == TSPGPU_F64, sets); e != hipSuccess) return hip_err(e);
     (void)hipEventRecord(s->e1, st);
     hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
     return 0;
@@ -810,7 +738,7 @@ static int begin_start(tspgpu_search *s)
     s->tails = 0;
     if (s->frontier) {
         hipError_t e = s->pristine ? hipSuccess : hipMemsetAsync(s->d_words + 8, 0, 16, s->ctx->stream);
-        if (e != hipSuccess) return herr(e);
+        if (e != hipSuccess) return hip_err(e);
         s->expand_steps = 0;
     }
     return 0;
@@ -900,14 +828,14 @@ static int search_start_fused(tspgpu_search *s, uint64_t cap, int ob[2])
     }
     hipError_t e = poison_chain(s, ob, cap);
     if (e == hipSuccess) e = zero_queue(s);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     SearchArgs a = args_of(s);
     a.fout = s->fb[ob[0]];
     a.fout_cap = (uint32_t)cap;
     a.out_count = reinterpret_cast<unsigned int *>(s->d_words + 11);
     a.overflow = reinterpret_cast<unsigned int *>(s->d_words + 13);
     e = launch_prologue1(a, s->dtype == TSPGPU_F64, seed_grid(s), sets);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     s->pending = s->local_items;
     return 0;
 }
@@ -931,7 +859,7 @@ static int frontier_step(tspgpu_search *s, uint64_t *pending)
             (void)hipEventRecord(s->e1, st);
             if (e == hipSuccess) e = hipMemsetAsync(s->d_words + 8, 0, 8, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return herr(e);
+            if (e != hipSuccess) return hip_err(e);
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
             s->tails = 0;
@@ -978,7 +906,7 @@ static int frontier_step(tspgpu_search *s, uint64_t *pending)
     unsigned long long *cnt = s->h_cnt ? s->h_cnt : local;
     if (e == hipSuccess) e = hipMemcpyAsync(cnt, s->d_words + 4, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
     ++s->rounds;
@@ -997,7 +925,7 @@ static int frontier_step(tspgpu_search *s, uint64_t *pending)
     if (kids && !s->seg_n.empty() && kids <= kAppendMax && s->fb[s->seg_buf.back()].cap >= s->seg_n.back() + kids) {
         e = hipMemcpyAsync(s->fb[s->seg_buf.back()] + s->seg_n.back(), s->fb[ob], kids * sizeof(PathItem),
                            hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return herr(e);
+        if (e != hipSuccess) return hip_err(e);
         s->seg_n.back() += kids;  // stream-ordered before the next step's launch
     } else if (kids) {
         s->seg_buf.push_back(ob);
@@ -1039,7 +967,7 @@ int tspgpu_search_step(tspgpu_search *s, uint64_t *pending)
         hipError_t e = hipMemcpyAsync(s->d_items[out] + s->pending, s->d_items[in] + take, carry * sizeof(SearchItem),
                                       hipMemcpyDeviceToDevice, s->ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
-        if (e != hipSuccess) return herr(e);
+        if (e != hipSuccess) return hip_err(e);
         s->pending += carry;
     }
     s->cur = out;
@@ -1184,7 +1112,7 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
     hipError_t e = s->pristine ? hipSuccess : hipMemsetAsync(s->d_words + 10, 0, 4 * sizeof(unsigned long long), st);
     if (e == hipSuccess && (!s->pristine || s->inc_shared))
         e = hipMemcpyAsync(s->d_words + 14, s->d_words + 1, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     // timed by the device clock when the fetch carries it (prologue start to
     // fetch start), else by events around the chain
     const bool fetch = s->fetch && s->h_stage;
@@ -1208,7 +1136,7 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
         }
     }
     if (!fuse) e = poison_chain(s, ob, kChainCap);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     // level l reads its input count from word 4 (the seeds, l = 0) or
     // 10 + l%3, writes 10 + (l+1)%3 and zeroes 10 + (l+2)%3
     if (fuse && hooks && 1 % every == 0) {  // (level 0 ran in the seeds' launch)
@@ -1255,7 +1183,7 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
         e = hipMemcpyAsync(h, s->d_words + 8, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     if (fetch) {  // seeds through the tail fold: device wall clock, prologue start to fetch start
         const unsigned long long *f = fetch_buf(s);
         const unsigned long long t0 = f[4 + 15], t1 = f[25];
@@ -1285,7 +1213,7 @@ static int run_chain(tspgpu_search *s, bool *done, int every = 0, tspgpu_level_h
     if (e == hipSuccess)
         e = hipMemcpyAsync(s->d_words + 1, s->d_words + 14, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = reset_tie_stats(s);
-    return herr(e);
+    return hip_err(e);
 }
 
 // Exhaustive enumeration in ONE launch (enum.hip): a lane per depth-(N-6)
@@ -1319,7 +1247,7 @@ static int run_enum(tspgpu_search *s, bool fetch)
     fetch = fetch && s->h_stage;
     if (e == hipSuccess && fetch) e = enqueue_fetch(s);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return herr(e);
+    if (e != hipSuccess) return hip_err(e);
     float ms = 0.f;
     if (grid > 0 && hipEventElapsedTime(&ms, s->e0, s->e1) == hipSuccess) s->ms += ms;
     s->pending = 0;
@@ -1404,7 +1332,7 @@ int tspgpu_search_tie_slot(tspgpu_search *s, uint64_t cost_bits, tspgpu_tie_slot
         if (e == hipSuccess)
             e = hipMemcpyAsync(h, tie_words(s), 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
-        if (e != hipSuccess) return herr(e);
+        if (e != hipSuccess) return hip_err(e);
         t = h;
     }
     const bool two = s->n - 1 > 20;
@@ -1466,7 +1394,7 @@ int tspgpu_search_reset_records(tspgpu_search *s, unsigned int capacity)
         if (e == hipSuccess) s->rec_cap = capacity;
     }
     if (e == hipSuccess) e = hipMemset(s->d_words + 3, 0, 8);
-    return herr(e);
+    return hip_err(e);
 }
 
 // the records of cost cost_bits among the `claimed` the kernels wrote
@@ -1479,7 +1407,7 @@ static int records_of(tspgpu_search *s, uint64_t claimed, uint64_t cost_bits, ts
         std::memcpy(h.data(), fetch_buf(s) + kFetchWords, sizeof(SearchRecord) * claimed);
     } else if (claimed) {
         hipError_t e = hipMemcpy(h.data(), s->d_rec, sizeof(SearchRecord) * claimed, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return herr(e);
+        if (e != hipSuccess) return hip_err(e);
     }
     int k = 0;
     for (const auto &r : h) {
@@ -1586,14 +1514,14 @@ static int search_solve(tspgpu_ctx *c, const void *dist, int dtype, int n, doubl
         if (e == hipSuccess)
             e = hipMemcpyAsync(tie_h, tie_words(s), 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                s->ctx->stream);
-        rc = herr(e);
+        rc = hip_err(e);
     }
     if (!rc && !s->fetched) {
         const unsigned k = std::min<unsigned>(kSpecRecs, s->rec_cap);
         spec.resize(k);
         hipError_t e = hipMemcpyAsync(spec.data(), s->d_rec, sizeof(SearchRecord) * k, hipMemcpyDeviceToHost,
                                       s->ctx->stream);
-        rc = herr(e);
+        rc = hip_err(e);
         if (!rc) rc = counters();  // (its synchronisation covers the record copy)
         spec_ok = !rc && recs <= k;
         specp = spec.data();
@@ -1626,8 +1554,8 @@ static int search_solve(tspgpu_ctx *c, const void *dist, int dtype, int n, doubl
         phases = 2;
         unsigned long long w = inc;
         rc = tspgpu_search_reset_records(s, (unsigned int)recs);
-        if (!rc) rc = herr(hipMemcpy(s->d_words + 1, &w, 8, hipMemcpyHostToDevice));
-        if (!rc) rc = herr(hipMemset(s->d_stats, 0, kStatBytes));
+        if (!rc) rc = hip_err(hipMemcpy(s->d_words + 1, &w, 8, hipMemcpyHostToDevice));
+        if (!rc) rc = hip_err(hipMemset(s->d_stats, 0, kStatBytes));
         if (!rc) rc = tspgpu_search_run_all(s);
         if (!rc) rc = counters();
         spec_ok = false;

@@ -18,14 +18,14 @@ struct Knob {
 
 // every knob the library reads (name, meaning at its one read site)
 Knob g_knobs[] = {
-    // K1 (tspgpu.cpp, read at context creation)
+    // K1 (ctx.cpp, read at context creation)
     {"K1", false, 0},              // force a variant: 2, 4 or 6 (below 4 -> 2; 5 = the fall-back of 6; above -> 6)
     {"TILED_CFG", false, 0},       // variant 6 configuration id (k1_cfg.h)
     {"K1_CHUNK", false, 0},        // tests: most blocks per variant-6 chunk (default 65536; below 1 ignored)
     {"WG_PER_CU", false, 0},       // workgroups per CU of the layer kernels
     {"THREADS", false, 0},         // threads per workgroup of the layer kernels
     {"LDS_TABLE_MAX_N", false, 0}, // largest N whose whole table lives in LDS
-    // device distance build (tspgpu.cpp, read at every build)
+    // device distance build (cities_abi.cpp, read at every build)
     {"DIST_FIX_CAP", false, 0},    // tests: entries of the fix-up list (default a quarter of the squares; below 1 ignored)
     // K1-wide (hkwide.hip)
     {"WIDE_PULL", false, 0},       // 1: per-destination layer form everywhere, 0: row-owner form

@@ -1,8 +1,9 @@
 // Handle lifetimes of the C ABI under host AddressSanitizer, on the GPU
 // (`make check-lifetime-asan`; tests/test_lifetime_gpu.py runs it).  The
-// library's host code (tspgpu.cpp, search_abi.cpp, search_host.cpp,
-// tuning.cpp) is compiled with -Xarch_host -fsanitize=address; the kernels
-// are the product's.  Checked:
+// library's host code (the Makefile's list of host translation units: ctx.cpp,
+// k1_launch.cpp, ragged_abi.cpp, cities_abi.cpp, search_abi.cpp,
+// search_host.cpp, tuning.cpp, sub_rows.cpp, ragged_plan.cpp) is compiled with
+// -Xarch_host -fsanitize=address; the kernels are the product's.  Checked:
 //   * round 4's segfault: tspgpu_ctx_destroy while searches are alive (the
 //     context freed the search pool through a null pointer, and a search
 //     destroyed afterwards dereferenced the freed context).  Now the context
