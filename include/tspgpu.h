@@ -367,7 +367,8 @@ typedef struct
 {
     uint64_t nodes;         /* search nodes: child extensions cost + d[last][next] with their bound test */
     uint64_t records;       /* complete tours recorded at cost <= incumbent (last phase) */
-    uint64_t optimal_tours; /* |O|: tours whose cost equals the optimum */
+    uint64_t optimal_tours; /* |O|: tours whose cost equals the optimum (0: not counted — the device tie
+                               rule answered without the records being read, or K1-wide did) */
     uint64_t items;         /* prefixes (work items) N!/(N-D)! */
     int depth;              /* prefix depth D */
     int phases;             /* 1, or 2 when the record buffer overflowed (second search, bound = optimum) */

@@ -56,3 +56,33 @@ def test_context_closed_before_searches():
     assert tspgpu.bits_cost(best, tspgpu.F64) == oc
     for S in reversed(shards):
         S.close()  # the last one releases the context
+
+
+def test_closed_contexts_leave_no_error_for_later_launches(gpu_ctx):
+    """Small copies go through a pool of pinned slots shared by the contexts of
+    a process (xfer.hip), each with an event behind its last upload.  Events
+    recorded only on the stream of a context closed since cannot be queried any
+    more; the failed query used to stay on the thread as its last error, and
+    the launch check of an unrelated later call (K1, K1-wide, K2) reported it
+    as a HIP failure, every time the pool came round to such a slot.  Three
+    short-lived contexts, then enough calls on the session's context to go
+    round the pool more than twice: every call succeeds with the oracle's
+    answer."""
+    rng = np.random.default_rng(12)
+    xy = rng.uniform(0, 1000, size=(4, 6, 2))
+    d = tspgpu.distance_matrix([[(b * 6 + i, xy[b, i, 0], xy[b, i, 1]) for i in range(6)] for b in range(4)])
+    want = [O.solve_block(d[b]) for b in range(4)]
+
+    def check(ctx):
+        cost, tour = ctx.solve_blocks(d)  # (an upload through a slot, two downloads)
+        assert [(cost[b], tour[b].tolist()) for b in range(4)] == want
+        c, t, _ = ctx.solve_instance(d[0])
+        assert (c, t.tolist()) == want[0]
+        c, t, _ = tspgpu.search_solve(ctx, d[1])
+        assert (c, t.tolist()) == want[1]
+
+    for _ in range(3):
+        with tspgpu.Context(device=0) as ctx:
+            check(ctx)
+    for _ in range(6):
+        check(gpu_ctx)

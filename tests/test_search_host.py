@@ -10,26 +10,7 @@ import pytest
 
 import oracle_py as O
 import tspgpu
-
-
-def left_fold(d, t):
-    """tsp.cpp's cost of the closed tour 0, t1..tN, 0 (IEEE double / int)."""
-    c = d.dtype.type(0)
-    prev = 0
-    for x in t:
-        c = c + d[prev, x]
-        prev = x
-    return c + d[prev, 0]
-
-
-def optimal_set(d):
-    """All tours whose left fold equals the optimum (brute force)."""
-    n = d.shape[0]
-    costs = {}
-    for p in itertools.permutations(range(1, n)):
-        costs[p] = left_fold(d, p)
-    opt = min(costs.values())
-    return opt, [p for p, c in costs.items() if c == opt]
+from rounding_ties import left_fold, optimal_set  # (moved there: the one copy)
 
 
 def records(opt_set, cost, dtype):

@@ -207,10 +207,11 @@ int tspgpu_stream_destroy(tspgpu_ctx *c, void *stream)
     // (a descriptor upload may sit on this stream: let it finish first)
     c->rg_desc.drain();
     c->bd_desc.drain();
+    // drained first: a pinned transfer slot whose last copy ran here is taken
+    // again once its event can no longer be queried (xfer.hip HipSlots::done)
+    (void)hipStreamSynchronize((hipStream_t)stream);
     if (c->k1_last_stream == (hipStream_t)stream) {
-        // the next launch must not wait on an event of a destroyed stream's queue:
-        // drain it and forget it
-        (void)hipStreamSynchronize((hipStream_t)stream);
+        // the next launch must not wait on an event of a destroyed stream's queue: forget it
         c->k1_launched = false;
         c->k1_last_stream = nullptr;
     }

@@ -71,7 +71,21 @@ struct HipSlots {
         }
         return true;
     }
-    bool done(hipEvent_t e) { return hipEventQuery(e) == hipSuccess; }
+    // A query that does not answer "complete" leaves its code as the thread's
+    // last error, and the hipGetLastError behind a later triple-chevron launch
+    // (K1, K1-wide, K2) would report it as that launch's failure: take it off
+    // the thread here.  Not ready: the slot stays pending.  Any other code: the
+    // event cannot be queried any more (seen for an event whose only record
+    // was on the stream of a context closed since; that stream was
+    // synchronised before it went, ctx.cpp tspgpu_ctx_release), so no copy
+    // through the slot is still running and the next copy records the event anew.
+    bool done(hipEvent_t e)
+    {
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) return true;
+        (void)hipGetLastError();
+        return q != hipErrorNotReady;
+    }
 };
 constexpr int kMaxPoolDevs = 64;
 using Pool = XferPool<HipSlots>;

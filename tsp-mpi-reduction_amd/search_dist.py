@@ -400,10 +400,10 @@ def solve_sharded(ctx, dist, group=None, depth: int = 0, device=None, exchange_e
                 recs_opt = None
                 if world == 1 and fast:
                     try:
-                        recs_opt = S.records(opt)
+                        recs_opt = _record_array(S, opt)
                     except tspgpu.TspGpuError:
                         recs_opt = None
-                if recs_opt:
+                if recs_opt is not None and len(recs_opt):
                     rc, t = tspgpu.tie_tour_records(ctx, dist, *w, recs_opt)
                 else:
                     rc, t = tspgpu.tie_tour_gpu(ctx, dist, *w) if ctx is not None else tspgpu.tie_tour(dist, *w)
@@ -456,11 +456,11 @@ def _records_winner(S, ctx, dist, opt, recs, nodes, allmin, collective, group):
 
     def local_records():
         try:
-            return S.records(opt), 0
+            return _record_array(S, opt), 0
         except tspgpu.TspGpuError as e:
             if e.code != -errno.EOVERFLOW:
                 raise
-            return [], 1
+            return (tspgpu.TourRecord * 0)(), 1
 
     phases = 1
     mine, lost = local_records()
@@ -482,7 +482,7 @@ def _records_winner(S, ctx, dist, opt, recs, nodes, allmin, collective, group):
                 raise tspgpu.TspGpuError(-errno.EOVERFLOW, "solve_sharded")
             _, t, _ = ctx.solve_instance(np.asarray(dist, dtype=np.float64))
             return t, phases, 1, nodes, 0
-    blob = np.frombuffer(b"".join(bytes(r) for r in mine), dtype=np.uint8) if mine else np.zeros(0, np.uint8)
+    blob = np.frombuffer(mine, dtype=np.uint8) if len(mine) else np.zeros(0, np.uint8)
     total_nodes = nodes
     if collective:
         parts = [None] * tdist.get_world_size(group)
@@ -495,16 +495,29 @@ def _records_winner(S, ctx, dist, opt, recs, nodes, allmin, collective, group):
             total_nodes = int(t.item())
     else:
         parts = [blob]
-    rsz = ctypes_sizeof_record()
-    allrec = []
-    for p in parts:
-        for i in range(0, len(p), rsz):
-            allrec.append(tspgpu.TourRecord.from_buffer_copy(bytes(p[i:i + rsz])))
+    # (one array for the host rule, no Python object per record: millions of tours can tie)
+    raw = b"".join(np.asarray(p, dtype=np.uint8).tobytes() for p in parts)
+    count = len(raw) // ctypes_sizeof_record()
+    allrec = (tspgpu.TourRecord * count).from_buffer_copy(raw)
     tour = tspgpu.select_tour(dist, allrec, tspgpu.bits_cost(opt, S.dtype))
-    return tour, phases, 0, total_nodes, len(allrec)
+    return tour, phases, 0, total_nodes, count
 
 
 def ctypes_sizeof_record() -> int:
     import ctypes
 
     return ctypes.sizeof(tspgpu.TourRecord)
+
+
+def _record_array(S, opt):
+    """The shard's records at the optimum as one ctypes array (a stand-in of
+    Search may return a list)."""
+    import ctypes
+
+    try:
+        recs = S.records(opt, as_array=True)
+    except TypeError:
+        recs = S.records(opt)
+    if isinstance(recs, ctypes.Array):
+        return recs
+    return (tspgpu.TourRecord * len(recs))(*recs)

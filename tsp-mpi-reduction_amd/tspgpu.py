@@ -954,11 +954,19 @@ def read_tsplib(path):
     return hdr.get("NAME", os.path.basename(path)), d.astype(np.int32)
 
 
+def _record_array(records):
+    """A list of TourRecord, or a ctypes array of them as it is (Search.records(as_array=True): no
+    per-record copy, millions of tied tours) -> the array to pass on."""
+    if isinstance(records, ctypes.Array):
+        return records
+    return (TourRecord * max(1, len(records)))(*records)
+
+
 def select_tour(dist, records, cost):
     """The DP's tie rule over the optimal set (tspgpu_select_tour)."""
     d, dt = _search_dist(dist)
     n = d.shape[0]
-    arr = (TourRecord * max(1, len(records)))(*records)
+    arr = _record_array(records)
     tour = np.zeros(n + 1, dtype=np.int32)
     rc = lib().tspgpu_select_tour(d.ctypes.data, dt, n, arr, len(records), cost_bits(cost, dt), _ip(tour))
     if rc:
@@ -1005,7 +1013,7 @@ def tie_tour_records(ctx, dist, w0: int, w1: int, cost, records):
     d, dt = _search_dist(dist)
     n = d.shape[0]
     tour = np.zeros(n + 1, dtype=np.int32)
-    arr = (TourRecord * max(1, len(records)))(*records)
+    arr = _record_array(records)
     rc = lib().tspgpu_tie_tour_records(ctx.handle if ctx is not None else None, d.ctypes.data, dt, n, w0, w1,
                                        cost_bits(cost, dt), arr, len(records), _ip(tour))
     return rc, tour
@@ -1115,16 +1123,18 @@ class Search:
     def reset_records(self, capacity: int = 0):
         self._check(lib().tspgpu_search_reset_records(self.handle, capacity), "tspgpu_search_reset_records")
 
-    def records(self, bits: int):
-        """Recorded tours whose cost word equals `bits` (list of TourRecord)."""
+    def records(self, bits: int, as_array: bool = False):
+        """Recorded tours whose cost word equals `bits`: a list of TourRecord,
+        or (as_array) the ctypes array itself, which select_tour and
+        tie_tour_records take without a copy per record."""
         cnt = ctypes.c_int()
         rc = lib().tspgpu_search_records(self.handle, bits, None, 0, ctypes.byref(cnt))
         if rc and rc != -errno.ENOSPC:
             raise TspGpuError(rc, "tspgpu_search_records")
-        arr = (TourRecord * max(1, cnt.value))()
-        self._check(lib().tspgpu_search_records(self.handle, bits, arr, cnt.value, ctypes.byref(cnt)),
-                    "tspgpu_search_records")
-        return list(arr[:cnt.value])
+        arr = (TourRecord * cnt.value)() if as_array else (TourRecord * max(1, cnt.value))()
+        self._check(lib().tspgpu_search_records(self.handle, bits, arr if cnt.value else None, cnt.value,
+                                                ctypes.byref(cnt)), "tspgpu_search_records")
+        return arr if as_array else list(arr[:cnt.value])
 
 
 def search_solve(ctx: "Context", dist, exhaustive: bool = False):
