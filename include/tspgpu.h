@@ -651,6 +651,87 @@ int tspgpu_pipeline_cities_ragged(tspgpu_ctx *ctx, const tspgpu_city *cities, co
                                   char *log, int logcap);
 
 /* ---------------------------------------------------------------------------
+ * Fixed-end shortest paths and the window refinement of a tour (DESIGN.md
+ * §6d; an extension: the reference has no counterpart).
+ *
+ * A path problem is a block of w cities, or a w x w row-major matrix D, with
+ * 4 <= w <= TSPGPU_MAX_CITIES (strict: 17).  Local city 0 is the fixed start,
+ * city w-1 the fixed end, the m = w-2 interior cities may be reordered.  The
+ * answer is the order 0, t1..tm, w-1 whose left fold
+ * ((D[0][t1] + D[t1][t2]) + ...) + D[tm][w-1] is minimal, DEFINED as what
+ * tspgpu_solve_blocks returns for the w-1 cities of the folded matrix P:
+ *   P[i][j] = D[i][j] for j >= 1,  P[i][0] = D[i][w-1] for i >= 1,  P[0][0] = 0
+ * cost bit for bit, the order K1's tour with its closing 0 replaced by w-1 (so
+ * ties break as K1 breaks them on P).  Only D[0][1..w-2], D[i][j] with i, j in
+ * 1..w-2 and D[1..w-2][w-1] are read: row w-1 and column 0 never are.
+ * Validation, status[b] and a bad block's outputs (cost NaN / -1, an order row
+ * of -1, neighbours solved) are the ragged contract above applied to P.
+ *
+ * Call-level errors (nothing launched, nothing written): -EINVAL for a NULL
+ * context, w outside [4, 20] (strict: 17), nblocks < 0, an unknown dtype, a
+ * NULL pointer with nblocks > 0.  nblocks == 0 returns 0.  Order rows have w
+ * entries.
+ * ------------------------------------------------------------------------- */
+/* Device-pointer form, asynchronous on `hip_stream` like
+ * tspgpu_solve_ragged_device.  d_dist: nblocks*w*w elements of dtype
+ * (TSPGPU_F64 / TSPGPU_I32), d_cost: nblocks of them, d_order: nblocks*w
+ * int32, d_status: nblocks int32. */
+int tspgpu_solve_paths_device(tspgpu_ctx *ctx, const void *d_dist, int dtype, int w, int nblocks, void *d_cost,
+                              int32_t *d_order, int32_t *d_status, void *hip_stream);
+/* Host-pointer form, synchronous.  Returns 0 however many blocks are bad. */
+int tspgpu_solve_paths(tspgpu_ctx *ctx, const void *dist, int dtype, int w, int nblocks, void *cost_out,
+                       int32_t *order_out, int32_t *status_out);
+/* From cities (nblocks*w tspgpu_city): the matrices come from the exact device
+ * build (the bits of tspgpu_distance_matrix), which synchronises the stream as
+ * tspgpu_distance_matrix_device does; the solve is left running. */
+int tspgpu_solve_paths_cities_device(tspgpu_ctx *ctx, const tspgpu_city *d_cities, int w, int nblocks,
+                                     double *d_cost, int32_t *d_order, int32_t *d_status, void *hip_stream);
+int tspgpu_solve_paths_cities(tspgpu_ctx *ctx, const tspgpu_city *cities, int w, int nblocks, double *cost_out,
+                              int32_t *order_out, int32_t *status_out);
+
+/* Window refinement.  A path is L >= 2 cities like BlockSolution.path; its two
+ * end cities never move (they need not be equal).  m, 2 <= m <= 18 (strict:
+ * 15), is the interior count of a window.  Pass p = 0, 1, ... uses the offset
+ * o_p = 0 (p even) or (m+1)/2 (p odd); its window k starts at position
+ * s = o_p + k(m+1) and covers s .. s+m+1, both ends fixed and shared with the
+ * neighbours, k < W_p = max(0, (L-1-o_p) / (m+1)).  Positions no window covers
+ * stay.  Every window is one path problem on tspgpu_distance_matrix of its
+ * m+2 cities; its old cost is the left fold of the identity order on that
+ * matrix; its interior is replaced by the solved order iff status == 0 and
+ * new < old strictly (a tie keeps the old order); gain_k = old - new for a
+ * replaced window, else 0.  The loop ends after pass p when p+1 == max_passes,
+ * or when p >= 1 and neither pass p nor pass p-1 replaced a window (an empty
+ * pass replaces none).  The result is a permutation of the input with both
+ * ends in place, and deterministic.  A path too short for any window
+ * (L < m+2) returns 0 with zero stats and the path untouched.
+ * -EINVAL: NULL context or path, L < 2, m out of range, max_passes < 1. */
+typedef struct
+{
+    int passes;           /* passes run (empty ones included) */
+    int64_t windows;      /* windows solved */
+    int64_t replaced;     /* windows whose interior was replaced */
+    int64_t skipped;      /* windows of status != 0 (left as they were) */
+    double gain;          /* left fold of gain_k on the host, in pass order then window order */
+    /* a measurement aid: device time (HIP events) summed over the passes of
+     * gather + distance build (the host's pow included), of K1 (with its
+     * validation gather and scatter) and of fold + apply */
+    double build_ms, k1_ms, fold_apply_ms;
+} tspgpu_refine_stats;
+/* In place on the device; synchronous (the host decides after every pass
+ * whether to stop, as tspgpu_reduce_device's merges need host decisions).
+ * stats may be NULL. */
+int tspgpu_refine_path_device(tspgpu_ctx *ctx, tspgpu_city *d_path, int L, int m, int max_passes,
+                              tspgpu_refine_stats *stats, void *hip_stream);
+/* Host form: path up, the device form on the context's stream, path_out (L
+ * cities; may be path itself) down. */
+int tspgpu_refine_path(tspgpu_ctx *ctx, const tspgpu_city *path, int L, int m, int max_passes, tspgpu_city *path_out,
+                       tspgpu_refine_stats *stats);
+/* The yardstick for before and after, on the host with glibc: the left fold,
+ * in path order, of the reference's distance() (assignment2.h:141-144) on
+ * consecutive cities.  L >= 1 (one city: 0). */
+int tspgpu_path_length(const tspgpu_city *path, int L, double *len);
+
+/* ---------------------------------------------------------------------------
  * Tuning and test knobs.  The defaults are the measured best; a knob changes
  * how the kernels run (K1 variant / configuration, buffer sizes, a bound
  * switched off for an A/B run, a fallback forced by a test), never the

@@ -53,6 +53,14 @@ int ragged_locked(tspgpu_ctx *c, const void *d_dist, int vbytes, RaggedPlan &pla
 int cities_args(const tspgpu_ctx *c, const void *cities, int n, const int32_t *ns, bool ragged, int nblocks,
                 int min_n, int *max_n, int64_t *ncities);
 
+// The matrices of nblocks blocks into d_dist on `stream` (c->mu held): n
+// cities each, or, with ns (a host array, every entry in [1, 20]), packed
+// ragged blocks of ns[b] cities (those above skip_above are not built).
+// Synchronises the stream once per build pass; the patch and finish kernels
+// are left running.
+int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
+                        hipStream_t stream, const int32_t *ns = nullptr, int skip_above = TSPGPU_MAX_CITIES);
+
 // One buffer of a host form: reserved, then copied to or from `host`
 struct HostCopy {
     DevBuf<char> *buf;

@@ -65,13 +65,11 @@ int upload_block_desc(tspgpu_ctx *c, const int32_t *ns, int skip_above, int nblo
     return 0;
 }
 
-// The matrices of nblocks blocks into d_dist on `stream` (c->mu held): n
-// cities each, or, with ns (a host array, every entry in [1, 20]), packed
-// ragged blocks of ns[b] cities (those above skip_above are not built).
-// Synchronises the stream once per build pass; the patch and finish kernels
-// are left running.
-int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
-                        hipStream_t stream, const int32_t *ns = nullptr, int skip_above = TSPGPU_MAX_CITIES)
+}  // namespace
+
+// (abi_internal.h: the window refinement builds its windows' matrices with it)
+int tspgpu::cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
+                                hipStream_t stream, const int32_t *ns, int skip_above)
 {
     using clk = std::chrono::steady_clock;
     if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
@@ -151,6 +149,8 @@ int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int n
     c->ct_pow_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
     return 0;
 }
+
+namespace {
 
 // Build the matrices into the context's buffer, then the ragged path (c->mu
 // held): n cities for every block, or, with ns, packed blocks of ns[b] cities

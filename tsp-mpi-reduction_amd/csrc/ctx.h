@@ -15,8 +15,9 @@
 using tspgpu_erased = std::unique_ptr<void, void (*)(void *)>;
 
 struct tspgpu_ctx {
-    // (members are used by ctx.cpp, k1_launch.cpp, ragged_abi.cpp and
-    // cities_abi.cpp for K1, search_abi.cpp for K2, merge.hip for K3)
+    // (members are used by ctx.cpp, k1_launch.cpp, ragged_abi.cpp,
+    // cities_abi.cpp and refine_abi.cpp for K1, search_abi.cpp for K2,
+    // merge.hip for K3)
     // Every buffer, event and cache below frees itself (hipbuf.h).  The stream
     // comes first so that it is destroyed after them all.
     tspgpu::Stream stream;
@@ -89,6 +90,18 @@ struct tspgpu_ctx {
     // kernels.  The device table is ordered like the fix-up list, behind
     // ev_k1_done.
     tspgpu::PinnedUpload bd_desc;
+    // Fixed-end paths and the window refinement (refine_abi.cpp, DESIGN.md
+    // §6d): the folded matrices K1 solves; a pass's packed windows, their
+    // matrices, K1's answers, the identity costs, gains and replaced flags
+    // with the pinned buffers these come down to; the host form's path; the
+    // five events that time a pass.  Per context and under the K1 ordering
+    // rule.
+    tspgpu::DevBuf<char> d_rf_fold, d_rf_cities, d_rf_path;
+    tspgpu::DevBuf<double> d_rf_dist, d_rf_cost, d_rf_old, d_rf_gain;
+    tspgpu::DevBuf<int32_t> d_rf_tour, d_rf_status, d_rf_flag;
+    tspgpu::Pinned<double> h_rf_gain;
+    tspgpu::Pinned<int32_t> h_rf_flag, h_rf_status;
+    tspgpu::Event ev_rf[5];
     // the last tspgpu_reduce_device's gather + summary + uniqueness kernels,
     // from HIP events (tspgpu_reduce_device_last_ms)
     double k3_gather_ms = 0.0;

@@ -35,6 +35,11 @@
 // ignored (TSP_STATS says so).
 // TSP_TOUR_OUT=FILE writes the merged tour's city ids, one per line (rank 0's
 // final path, closing city included), in either mode; not with TSP_HOST_MERGE.
+// TSP_REFINE=m (with TSP_TOUR_OUT) refines that tour on the GPU before it is
+// written (tspgpu_refine_path: windows of m interior cities solved exactly,
+// at most TSP_REFINE_PASSES passes, default 8) and adds one line on stderr:
+// the tour's length before and after and what the passes did.  It runs after
+// the reference's clock has stopped; stdout stays the reference's.
 //
 // Deviations (documented in DESIGN.md), all where the reference is undefined:
 // n < 2, numBlocks < 1 or numBlocks < P exit 2 with a message on stderr
@@ -493,7 +498,11 @@ int main(int argc, char **argv)
     }
     std::fputs(log.data(), stdout);
     clock_gettime(CLOCK_MONOTONIC_RAW, &ts_merge1);
-    if (tour_file && merged_len >= 0) {
+    const int refine_m = env_int("TSP_REFINE", 0);
+    const bool refine = refine_m > 0 && tour_file && merged_len >= 0 && kept;
+    if (refine) {
+        // (refined and written below, once the clock has stopped)
+    } else if (tour_file && merged_len >= 0) {
         const int wrc = write_tour(tour_file, merged.data(), merged_len);
         if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));
     } else if (tour_file) {
@@ -507,6 +516,26 @@ int main(int argc, char **argv)
     // the device context is torn down after the clock, like the reference's
     // MPI_Finalize after its end time (tsp.cpp:358-366)
     std::fflush(stdout);
+    if (refine) {
+        double before = 0.0, after = 0.0;
+        tspgpu_refine_stats rs;
+        std::memset(&rs, 0, sizeof rs);
+        (void)tspgpu_path_length(merged.data(), merged_len, &before);
+        const int rrc = tspgpu_refine_path(kept, merged.data(), merged_len, refine_m, env_int("TSP_REFINE_PASSES", 8),
+                                           merged.data(), &rs);
+        (void)tspgpu_path_length(merged.data(), merged_len, &after);
+        if (rrc)
+            std::fprintf(stderr, "tsp: TSP_REFINE=%d failed, the tour is written as merged: %s (%d)\n", refine_m,
+                         tspgpu_strerror(rrc), rrc);
+        else
+            std::fprintf(stderr,
+                         "tsp refine: m %d | tour length %f -> %f | %d passes, %lld windows solved, %lld replaced, "
+                         "%lld skipped, gain %f\n",
+                         refine_m, before, after, rs.passes, (long long)rs.windows, (long long)rs.replaced,
+                         (long long)rs.skipped, rs.gain);
+        const int wrc = write_tour(tour_file, merged.data(), merged_len);
+        if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));
+    }
     if (kept) tspgpu_ctx_destroy(kept);
     kept = nullptr;
     // opt-in statistics on stderr (SURVEY.md §5 "Metrics": stdout stays the

@@ -50,6 +50,9 @@ EXPORTED_SYMBOLS = (
     # ragged blocks end to end: packed cities of different block sizes -> distances, K1, K3, the merged tour
     "tspgpu_distance_matrix_ragged_device", "tspgpu_solve_cities_ragged_device", "tspgpu_solve_cities_ragged",
     "tspgpu_reduce_ragged_device", "tspgpu_reduce_ragged", "tspgpu_pipeline_cities_ragged",
+    # fixed-end shortest paths (K1 on the folded matrix) and the window refinement of a tour on the device
+    "tspgpu_solve_paths", "tspgpu_solve_paths_device", "tspgpu_solve_paths_cities", "tspgpu_solve_paths_cities_device",
+    "tspgpu_refine_path", "tspgpu_refine_path_device", "tspgpu_path_length",
     # tuning / test knobs
     "tspgpu_tuning_set", "tspgpu_tuning_clear",
 )
@@ -80,6 +83,16 @@ class TieSlot(ctypes.Structure):
     """tspgpu_tie_slot: a shard's least tie key at one cost."""
     _fields_ = [("w0", ctypes.c_uint64), ("w1", ctypes.c_uint64), ("found", ctypes.c_int),
                 ("overflow", ctypes.c_int)]
+
+
+class RefineStats(ctypes.Structure):
+    """tspgpu_refine_stats: what a window refinement did, and its device times."""
+    _fields_ = [("passes", ctypes.c_int), ("windows", ctypes.c_int64), ("replaced", ctypes.c_int64),
+                ("skipped", ctypes.c_int64), ("gain", ctypes.c_double), ("build_ms", ctypes.c_double),
+                ("k1_ms", ctypes.c_double), ("fold_apply_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 LEVEL_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p)
@@ -224,6 +237,14 @@ def lib():
                                            ctypes.c_char_p, ctypes.c_int]
         L.tspgpu_pipeline_cities_ragged.argtypes = [vp, cp, ip, ctypes.c_int, ctypes.c_int, dp, cp, ctypes.c_int,
                                                     intp, ctypes.c_char_p, ctypes.c_int]
+        L.tspgpu_solve_paths.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ip, ip]
+        L.tspgpu_solve_paths_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+        L.tspgpu_solve_paths_cities.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, dp, ip, ip]
+        L.tspgpu_solve_paths_cities_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+        rsp = ctypes.POINTER(RefineStats)
+        L.tspgpu_refine_path.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cp, rsp]
+        L.tspgpu_refine_path_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, rsp, vp]
+        L.tspgpu_path_length.argtypes = [cp, ctypes.c_int, dp]
         _lib = L
     return _lib
 
@@ -322,6 +343,18 @@ def distance_matrix_array(arr, n: int, B: int) -> np.ndarray:
     if rc:
         raise TspGpuError(rc, "tspgpu_distance_matrix")
     return d
+
+
+def path_length(path) -> float:
+    """tspgpu_path_length: the left fold, in path order, of the reference's
+    distance() on consecutive cities of a path (list of (id, x, y)); host
+    glibc.  The yardstick for refine_path's before and after."""
+    arr, L, _ = cities_array([path])
+    out = ctypes.c_double()
+    rc = lib().tspgpu_path_length(arr, L, ctypes.byref(out))
+    if rc:
+        raise TspGpuError(rc, "tspgpu_path_length")
+    return out.value
 
 
 def validate(dist: np.ndarray, strict: bool = False) -> int:
@@ -701,14 +734,91 @@ class Context:
         self._check(lib().tspgpu_reduce_device_last_ms(self.handle, ctypes.byref(ms)), "tspgpu_reduce_device_last_ms")
         return ms.value
 
-    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None):
+    # ---- fixed-end shortest paths and the window refinement of a tour ----
+
+    def solve_paths(self, dist: np.ndarray):
+        """tspgpu_solve_paths: dist (B, w, w) float64 or int32, city 0 the fixed
+        start and city w-1 the fixed end of every block -> (cost (B,) of dist's
+        type, order (B, w) int32: 0, t1..tm, w-1, status (B,) int32).  Status
+        0: the minimal left fold and K1's tie-broken order on the folded
+        matrix; else a negative errno, cost NaN / -1 and an order row of -1.
+        Row w-1 and column 0 of a matrix are never read."""
+        dist = np.ascontiguousarray(dist)
+        if dist.dtype != np.int32:
+            dist = np.ascontiguousarray(dist, dtype=np.float64)
+        B, w, _ = dist.shape
+        cost = np.zeros(B, dtype=dist.dtype)
+        order = np.full((B, w), -1, dtype=np.int32)
+        status = np.zeros(B, dtype=np.int32)
+        self._check(lib().tspgpu_solve_paths(self.handle, dist.ctypes.data, I32 if dist.dtype == np.int32 else F64, w,
+                                             B, cost.ctypes.data, _ip(order), _ip(status)), "tspgpu_solve_paths")
+        return cost, order, status
+
+    def solve_paths_device(self, d_dist_ptr: int, dtype: int, w: int, nblocks: int, d_cost_ptr: int, d_order_ptr: int,
+                           d_status_ptr: int, stream_ptr: int = 0):
+        """tspgpu_solve_paths_device: device pointers for dist (B*w*w of dtype),
+        cost, order (B x w int32) and status.  Asynchronous on stream_ptr."""
+        self._check(lib().tspgpu_solve_paths_device(self.handle, d_dist_ptr, dtype, w, nblocks, d_cost_ptr,
+                                                    d_order_ptr, d_status_ptr, stream_ptr or None),
+                    "tspgpu_solve_paths_device")
+
+    def solve_paths_cities(self, blocks):
+        """tspgpu_solve_paths_cities: blocks of w cities (lists of (id, x, y), or
+        a (ctypes City array, w, B) triple), the first the fixed start and the
+        last the fixed end -> (cost, order, status) as solve_paths, on the
+        matrices of distance_matrix() built on the device."""
+        arr, w, B = blocks if isinstance(blocks, tuple) else cities_array(blocks)
+        cost = np.zeros(B, dtype=np.float64)
+        order = np.full((B, w), -1, dtype=np.int32)
+        status = np.zeros(B, dtype=np.int32)
+        self._check(lib().tspgpu_solve_paths_cities(self.handle, arr, w, B, _dp(cost), _ip(order), _ip(status)),
+                    "tspgpu_solve_paths_cities")
+        return cost, order, status
+
+    def solve_paths_cities_device(self, d_cities_ptr: int, w: int, nblocks: int, d_cost_ptr: int, d_order_ptr: int,
+                                  d_status_ptr: int, stream_ptr: int = 0):
+        """tspgpu_solve_paths_cities_device: B*w City structs on the device ->
+        cost, order and status on the device.  Synchronises the stream as
+        distance_matrix_device does; the solve is left running."""
+        self._check(lib().tspgpu_solve_paths_cities_device(self.handle, d_cities_ptr, w, nblocks, d_cost_ptr,
+                                                           d_order_ptr, d_status_ptr, stream_ptr or None),
+                    "tspgpu_solve_paths_cities_device")
+
+    def refine_path(self, path, interior: int = 15, max_passes: int = 8):
+        """tspgpu_refine_path: a path (list of (id, x, y), closing city included
+        or not) -> (refined path, stats dict).  The path is tiled with windows
+        of `interior` cities between two fixed ones, every window is solved
+        exactly and the strictly shorter orders are spliced back; odd passes
+        shift the windows by half.  Both end cities stay."""
+        arr, L, _ = cities_array([path])
+        out = (City * max(1, L))()
+        st = RefineStats()
+        self._check(lib().tspgpu_refine_path(self.handle, arr, L, interior, max_passes, out, ctypes.byref(st)),
+                    "tspgpu_refine_path")
+        return [(out[i].id, out[i].x, out[i].y) for i in range(L)], st.as_dict()
+
+    def refine_path_device(self, d_path_ptr: int, L: int, interior: int = 15, max_passes: int = 8,
+                           stream_ptr: int = 0):
+        """tspgpu_refine_path_device: L City structs on the device, refined in
+        place; synchronous -> stats dict."""
+        st = RefineStats()
+        self._check(lib().tspgpu_refine_path_device(self.handle, d_path_ptr, L, interior, max_passes, ctypes.byref(st),
+                                                    stream_ptr or None), "tspgpu_refine_path_device")
+        return st.as_dict()
+
+    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0):
         """tspgpu_pipeline_cities: blocks (lists of (id, x, y), or a (ctypes City
         array, n, B) triple) -> (final cost, log text, merged tour as a list of
         (id, x, y)): block search and merges on the device, only the costs
         visit the host in between.  path_cap None: room for (2 + log2 nprocs)
         times the cities, so one run gives the tour; only if that is ever
         short does the whole pipeline run a second time with the reported
-        length."""
+        length.  refine = m > 0: refine_path(tour, m) on the merged tour ->
+        (final cost, log text, refined tour, stats dict); the cost and the log
+        stay the reference's."""
+        if refine:
+            final, log, path = self.pipeline_cities(blocks, nprocs, path_cap)
+            return (final, log) + self.refine_path(path, refine)
         arr, n, B = blocks if isinstance(blocks, tuple) else cities_array(blocks)
 
         def call(out, cap):
@@ -805,11 +915,14 @@ class Context:
         return self._path_result("tspgpu_reduce_ragged", call, path_cap,
                                  self._tour_capacity(1, int(lens.sum()), nprocs))
 
-    def pipeline_cities_ragged(self, blocks, nprocs: int, path_cap: int | None = None):
+    def pipeline_cities_ragged(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0):
         """tspgpu_pipeline_cities_ragged: blocks of different sizes (lists of
         (id, x, y), or a (ctypes City array, n) pair) -> (final cost, log
-        text, merged tour as a list of (id, x, y)); path_cap as for
+        text, merged tour as a list of (id, x, y)); path_cap and refine as for
         pipeline_cities."""
+        if refine:
+            final, log, path = self.pipeline_cities_ragged(blocks, nprocs, path_cap)
+            return (final, log) + self.refine_path(path, refine)
         arr, n = blocks if isinstance(blocks, tuple) else cities_array_ragged(blocks)
         n = self._ns(n)
         total = int(sum(tour_length(int(k)) for k in n))
