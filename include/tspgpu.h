@@ -732,6 +732,75 @@ int tspgpu_refine_path(tspgpu_ctx *ctx, const tspgpu_city *path, int L, int m, i
 int tspgpu_path_length(const tspgpu_city *path, int L, double *len);
 
 /* ---------------------------------------------------------------------------
+ * 2-opt with a neighbour grid (an extension: the reference has
+ * no counterpart).  The stage in front of the window refinement: it repairs
+ * what no window can hold, two edges close in the plane and far apart in tour
+ * order.  The whole contract is below; tests/two_opt_model.py is the same in
+ * Python, and the device matches it bit for bit.
+ *
+ * A path is L cities like BlockSolution.path, 1 <= L <= 2^30.  Positions 0
+ * and L-1 never move and need not be equal.  "City" means the index a city
+ * had in the input; coincident and duplicate cities are ordinary cities.
+ *
+ * Distance.  d(a,b) = sqrt(dx*dx + dy*dy), dx = a.x - b.x, dy = a.y - b.y, in
+ * f64, every operation rounded on its own (no contraction), sqrt correctly
+ * rounded.  It is the search's metric, not the reference's pow form:
+ * tspgpu_path_length stays the yardstick for before and after.
+ *
+ * Validation, before anything is written.  -EINVAL: a NULL context or path,
+ * L < 1 (or above 2^30), ring outside 1..4, max_passes < 1, any non-finite
+ * coordinate.  -ERANGE: with ex = xmax - xmin and ey = ymax - ymin over all L
+ * cities, ex, ey or ex*ex + ey*ey not finite.  L < 4 (after these checks): 0
+ * with passes = 0 and the path untouched.  On an error neither the path nor
+ * *stats is written.
+ *
+ * Grid, built once per call (cities do not move, only their positions).  g
+ * is the largest integer with 2*g*g <= L, clamped to [1, 2048].  The cell of
+ * a city is cx = min(g-1, (int)(((x - xmin) / ex) * g)), 0 when ex == 0, and
+ * cy likewise on y: an IEEE division, then the product.  N(c) is every city,
+ * c included, whose cell is within `ring` cells of c's in both coordinates,
+ * clipped at the border; N is symmetric.
+ *
+ * Moves.  With p the current order, move (i, j) is defined for 0 <= i,
+ * i+2 <= j <= L-2.  With a = p[i], b = p[i+1], c = p[j], e = p[j+1],
+ *   gain = (d(a,b) + d(c,e)) - (d(a,c) + d(b,e))
+ * in exactly that order of operations, and applying it reverses positions
+ * i+1..j.  The candidates of position i are the j with c in N(a) or e in
+ * N(b); a j found both ways is one candidate.  The best move of i is the
+ * largest gain among its candidates with gain > 0, the smallest j on equal
+ * gains; it may not exist.  Nothing prunes the candidates.
+ *
+ * A pass.  (1) The best move of every i, all under the order at the start of
+ * the pass.  (2) Sort the existing ones by (gain descending, i ascending).
+ * (3) In that order accept a move iff its edge range [i, j] is disjoint from
+ * that of every move accepted before: (i, j) and (j+1, j') are compatible,
+ * sharing edge j is not.  (4) gain = gain + g_k for every accepted move in
+ * acceptance order, a left fold.  (5) Apply all accepted reversals.  A pass
+ * that accepts nothing is counted and ends the call, as does reaching
+ * max_passes.  Every choice is a total order, so the result is a function of
+ * the input alone: a permutation of it with both ends in place.
+ * ------------------------------------------------------------------------- */
+typedef struct
+{
+    int passes;         /* passes run (the last, empty one included) */
+    int64_t candidates; /* best moves sent to the selection, summed over the passes */
+    int64_t moves;      /* moves accepted and applied */
+    double gain;        /* the left fold of the accepted gains */
+    /* a measurement aid: device time (HIP events) of bounds + grid build, of
+     * the searches and of the applies, and the host's time in the selection,
+     * each summed over the passes */
+    double grid_ms, search_ms, select_ms, apply_ms;
+} tspgpu_two_opt_stats;
+/* In place on the device; synchronous (the host selects after every pass).
+ * stats may be NULL. */
+int tspgpu_two_opt_path_device(tspgpu_ctx *ctx, tspgpu_city *d_path, int L, int ring, int max_passes,
+                               tspgpu_two_opt_stats *stats, void *hip_stream);
+/* Host form: path up, the device form on the context's stream, path_out (L
+ * cities; may be path itself) down. */
+int tspgpu_two_opt_path(tspgpu_ctx *ctx, const tspgpu_city *path, int L, int ring, int max_passes,
+                        tspgpu_city *path_out, tspgpu_two_opt_stats *stats);
+
+/* ---------------------------------------------------------------------------
  * Tuning and test knobs.  The defaults are the measured best; a knob changes
  * how the kernels run (K1 variant / configuration, buffer sizes, a bound
  * switched off for an A/B run, a fallback forced by a test), never the

@@ -1,0 +1,161 @@
+"""2-opt stage timing and gain probe (development aid).
+
+    two_opt_time.py [--repeats R] [--warmup W] [--max-passes P] [--shapes ..] [--rings ..] [--out FILE] [--append]
+
+For the reference generator's batches 16 x 16384 and 8 x 1024 (`./tsp n B 1000
+1000`, one rank): the merged tour of tspgpu_pipeline_cities, then
+tspgpu_two_opt_path on it with ring 1, 2 and 3, run to its stop (max_passes is
+generous).  Reported per (shape, ring):
+
+  passes to the stop, candidates sent to the selection, moves applied;
+  tspgpu_path_length before and after 2-opt, after tspgpu_refine_path(m = 15)
+  alone and after 2-opt + that refinement (which must be strictly shorter than
+  the refinement alone: the run asserts it);
+  wall time of the 2-opt call (host form: the tour goes up and comes back),
+  median of R runs after W warm-ups, and per pass;
+  the library's phase times: grid (bounds + grid build, once), search and
+  apply (HIP events, summed over the passes), select (host clock), and what
+  is left of the wall time: the per-pass copies and synchronisations;
+  the wall time of the pipeline_cities call that made the tour, measured in
+  the same process, for scale.
+
+The stage is deterministic: every repeat must return the same tour, and the
+run checks it.  A last line of JSON per invocation.
+profiles/two_opt/two_opt_time.txt is this report (--out; --append adds one
+shape's run to the file of another's)."""
+import argparse, ctypes, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "tsp-mpi-reduction_amd"), ROOT]
+import numpy as np
+import tspgpu
+from bench import Shard  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=1)
+ap.add_argument("--max-passes", type=int, default=100000)
+ap.add_argument("--interior", type=int, default=15, help="m of the refinement the stage is composed with")
+ap.add_argument("--out", default=None, help="also write the report to this file")
+ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
+ap.add_argument("--shapes", default="16x16384,8x1024", help="n x B, comma separated")
+ap.add_argument("--rings", default="1,2,3")
+args = ap.parse_args()
+
+lines = []
+
+
+def say(text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+ctx = tspgpu.Context(device=0)
+L_ = tspgpu.lib()
+cu, name = ctx.device_info()
+cp = ctypes.POINTER(tspgpu.City)
+say(f"device: {name}; repeats={args.repeats} warmup={args.warmup} max_passes={args.max_passes} "
+    f"refine m={args.interior}")
+
+
+def wall(fn):
+    t0 = time.perf_counter()
+    fn()
+    return 1e3 * (time.perf_counter() - t0)
+
+
+def length(arr, L):
+    out = ctypes.c_double()
+    assert L_.tspgpu_path_length(arr.ctypes.data_as(cp), L, ctypes.byref(out)) == 0
+    return out.value
+
+
+def refined(src, L):
+    out = np.zeros(L, dtype=tspgpu.CITY_DTYPE)
+    st = tspgpu.RefineStats()
+    rc = L_.tspgpu_refine_path(ctx.handle, src.ctypes.data_as(cp), L, args.interior, 64, out.ctypes.data_as(cp),
+                               ctypes.byref(st))
+    assert rc == 0, rc
+    return length(out, L)
+
+
+def run(n, B):
+    case = f"{n}x{B}"
+    sh = Shard(n, B, 0, B)
+    cap = B * n + 1
+    tour = np.zeros(cap, dtype=tspgpu.CITY_DTYPE)
+    log = ctypes.create_string_buffer(1 << 20)
+    final, plen = ctypes.c_double(), ctypes.c_int()
+
+    def pipeline():
+        rc = L_.tspgpu_pipeline_cities(ctx.handle, sh.arr, n, B, 1, ctypes.byref(final), tour.ctypes.data_as(cp), cap,
+                                       ctypes.byref(plen), log, len(log))
+        assert rc == 0, rc
+
+    for _ in range(args.warmup):
+        pipeline()
+    pipe_ms = [wall(pipeline) for _ in range(args.repeats)]
+    L = plen.value
+    before = length(tour, L)
+    alone = refined(tour, L)
+    res = {"tour_cities": L, "pipeline_cities_ms": {"median": float(np.median(pipe_ms)),
+                                                    "repeats": [round(x, 3) for x in pipe_ms]},
+           "length_before": before, "length_refine_alone": alone, "pipeline_cost": final.value}
+    say(f"{case} pipeline_cities: median {np.median(pipe_ms):.3f} ms ({' '.join(f'{x:.2f}' for x in pipe_ms)}); "
+        f"tour {L} cities, path_length {before:.6f}; after refine(m={args.interior}) alone {alone:.6f} "
+        f"({100.0 * (before - alone) / before:.3f}% shorter)")
+    for ring in map(int, args.rings.split(",")):
+        out = np.zeros(L, dtype=tspgpu.CITY_DTYPE)
+        st = tspgpu.TwoOptStats()
+
+        def two_opt():
+            rc = L_.tspgpu_two_opt_path(ctx.handle, tour.ctypes.data_as(cp), L, ring, args.max_passes,
+                                        out.ctypes.data_as(cp), ctypes.byref(st))
+            assert rc == 0, rc
+
+        for _ in range(args.warmup):
+            two_opt()
+        two_opt()
+        first = out.view(np.uint8).copy()  # (raw bytes: a structured copy leaves the padding undefined)
+        ms, ph = [], []
+        for _ in range(args.repeats):
+            ms.append(wall(two_opt))
+            ph.append((st.grid_ms, st.search_ms, st.select_ms, st.apply_ms))
+            assert np.array_equal(out.view(np.uint8), first)  # deterministic
+        s = st.as_dict()
+        after = length(out, L)
+        both = refined(out, L)
+        assert np.array_equal(np.sort(out["id"]), np.sort(tour["id"][:L])) and out[0] == tour[0] and out[L - 1] == tour[L - 1]
+        assert both < alone, (both, alone)  # the one condition: the two compose
+        p = max(1, s["passes"])
+        med = float(np.median(ms))
+        grid, search, select, apply_ = (float(np.median([e[i] for e in ph])) for i in range(4))
+        rest = med - (grid + search + select + apply_)
+        res[f"ring={ring}"] = {"passes": s["passes"], "candidates": s["candidates"], "moves": s["moves"],
+                               "gain": s["gain"], "length_after": after, "length_after_refine": both,
+                               "shorter_percent": 100.0 * (before - after) / before,
+                               "shorter_percent_with_refine": 100.0 * (before - both) / before,
+                               "wall_ms": {"median": med, "repeats": [round(x, 3) for x in ms]},
+                               "wall_ms_per_pass": med / p,
+                               "phase_ms": {"grid": grid, "search": search, "select": select, "apply": apply_,
+                                            "copies_and_syncs": rest},
+                               "stopped_by_rule": s["passes"] < args.max_passes}
+        say(f"{case} ring={ring}: {s['passes']} passes{'' if s['passes'] < args.max_passes else ' (max_passes reached)'}, "
+            f"{s['candidates']} candidates, {s['moves']} moves | path_length {before:.6f} -> {after:.6f} "
+            f"({100.0 * (before - after) / before:.3f}% shorter; gain {s['gain']:.6f}) -> {both:.6f} after "
+            f"refine(m={args.interior}) ({100.0 * (before - both) / before:.3f}%)")
+        say(f"{case} ring={ring}: wall median {med:.3f} ms ({' '.join(f'{x:.2f}' for x in ms)}) = {med / p:.3f} ms/pass; "
+            f"phase ms: grid {grid:.3f}, search {search:.3f}, select (host) {select:.3f}, apply {apply_:.3f}, "
+            f"copies + syncs {rest:.3f}; {med / np.median(pipe_ms):.2f} x the pipeline_cities call")
+    return res
+
+
+result = {"device": name, "repeats": args.repeats, "max_passes": args.max_passes, "refine_m": args.interior}
+for shape in args.shapes.split(","):
+    n, B = map(int, shape.split("x"))
+    result[shape] = run(n, B)
+say(json.dumps(result))
+ctx.close()
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a" if args.append else "w") as f:
+        f.write("\n".join(lines) + "\n")

@@ -16,8 +16,8 @@ using tspgpu_erased = std::unique_ptr<void, void (*)(void *)>;
 
 struct tspgpu_ctx {
     // (members are used by ctx.cpp, k1_launch.cpp, ragged_abi.cpp,
-    // cities_abi.cpp and refine_abi.cpp for K1, search_abi.cpp for K2,
-    // merge.hip for K3)
+    // cities_abi.cpp, refine_abi.cpp and two_opt_abi.cpp for K1 and the tour
+    // stages, search_abi.cpp for K2, merge.hip for K3)
     // Every buffer, event and cache below frees itself (hipbuf.h).  The stream
     // comes first so that it is destroyed after them all.
     tspgpu::Stream stream;
@@ -102,6 +102,21 @@ struct tspgpu_ctx {
     tspgpu::Pinned<double> h_rf_gain;
     tspgpu::Pinned<int32_t> h_rf_flag, h_rf_status;
     tspgpu::Event ev_rf[5];
+    // 2-opt with a neighbour grid (two_opt_abi.cpp): the host
+    // form's path and the copy of the input the final order is gathered
+    // from; the state by position (ord, pos, px, py); the grid (cell of a
+    // city, the cells' starts and fill cursors, the scan's partial sums, the
+    // cell-sorted x, y, city); a pass's candidates and accepted moves (i, j,
+    // swap prefix) with their pinned twins; the bounds and the candidate
+    // counter as one block of words; the six events that time the grid
+    // build, a search and an apply.  Per context and under the K1 ordering
+    // rule.
+    tspgpu::DevBuf<char> d_to_path, d_to_in, d_to_cand, d_to_words;
+    tspgpu::DevBuf<int32_t> d_to_ord, d_to_pos, d_to_cell, d_to_start, d_to_cursor, d_to_sums, d_to_city, d_to_acc;
+    tspgpu::DevBuf<double> d_to_px, d_to_py, d_to_cx, d_to_cy;
+    tspgpu::Pinned<char> h_to_cand, h_to_words;
+    tspgpu::Pinned<int32_t> h_to_acc;
+    tspgpu::Event ev_to[6];
     // the last tspgpu_reduce_device's gather + summary + uniqueness kernels,
     // from HIP events (tspgpu_reduce_device_last_ms)
     double k3_gather_ms = 0.0;

@@ -40,6 +40,12 @@
 // at most TSP_REFINE_PASSES passes, default 8) and adds one line on stderr:
 // the tour's length before and after and what the passes did.  It runs after
 // the reference's clock has stopped; stdout stays the reference's.
+// TSP_TWO_OPT=passes (with TSP_TOUR_OUT) runs 2-opt between spatial
+// neighbours on that tour first (tspgpu_two_opt_path: at most `passes` passes,
+// cells within TSP_TWO_OPT_RING of each other, default 2), before TSP_REFINE
+// if both are set and like it after the clock, with one stderr line of its
+// own: length before and after, passes, moves, gain.  If it fails the tour
+// goes on as merged.
 //
 // Deviations (documented in DESIGN.md), all where the reference is undefined:
 // n < 2, numBlocks < 1 or numBlocks < P exit 2 with a message on stderr
@@ -499,9 +505,12 @@ int main(int argc, char **argv)
     std::fputs(log.data(), stdout);
     clock_gettime(CLOCK_MONOTONIC_RAW, &ts_merge1);
     const int refine_m = env_int("TSP_REFINE", 0);
-    const bool refine = refine_m > 0 && tour_file && merged_len >= 0 && kept;
-    if (refine) {
-        // (refined and written below, once the clock has stopped)
+    const int two_opt_passes = env_int("TSP_TWO_OPT", 0);
+    const bool improvable = tour_file && merged_len >= 0 && kept;
+    const bool refine = refine_m > 0 && improvable;
+    const bool two_opt = two_opt_passes > 0 && improvable;
+    if (refine || two_opt) {
+        // (improved and written below, once the clock has stopped)
     } else if (tour_file && merged_len >= 0) {
         const int wrc = write_tour(tour_file, merged.data(), merged_len);
         if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));
@@ -516,6 +525,25 @@ int main(int argc, char **argv)
     // the device context is torn down after the clock, like the reference's
     // MPI_Finalize after its end time (tsp.cpp:358-366)
     std::fflush(stdout);
+    if (two_opt) {
+        double before = 0.0, after = 0.0;
+        const int ring = env_int("TSP_TWO_OPT_RING", 2);
+        tspgpu_two_opt_stats ts;
+        std::memset(&ts, 0, sizeof ts);
+        (void)tspgpu_path_length(merged.data(), merged_len, &before);
+        const int trc = tspgpu_two_opt_path(kept, merged.data(), merged_len, ring, two_opt_passes, merged.data(), &ts);
+        (void)tspgpu_path_length(merged.data(), merged_len, &after);
+        if (trc)
+            std::fprintf(stderr, "tsp: TSP_TWO_OPT=%d failed, the tour is written as merged: %s (%d)\n", two_opt_passes,
+                         tspgpu_strerror(trc), trc);
+        else
+            std::fprintf(stderr, "tsp two-opt: ring %d | tour length %f -> %f | %d passes, %lld moves, gain %f\n", ring,
+                         before, after, ts.passes, (long long)ts.moves, ts.gain);
+        if (!refine) {
+            const int wrc = write_tour(tour_file, merged.data(), merged_len);
+            if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));
+        }
+    }
     if (refine) {
         double before = 0.0, after = 0.0;
         tspgpu_refine_stats rs;

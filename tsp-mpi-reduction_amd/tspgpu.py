@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = (
     # fixed-end shortest paths (K1 on the folded matrix) and the window refinement of a tour on the device
     "tspgpu_solve_paths", "tspgpu_solve_paths_device", "tspgpu_solve_paths_cities", "tspgpu_solve_paths_cities_device",
     "tspgpu_refine_path", "tspgpu_refine_path_device", "tspgpu_path_length",
+    # 2-opt with a neighbour grid on a path, the stage in front of the window refinement
+    "tspgpu_two_opt_path", "tspgpu_two_opt_path_device",
     # tuning / test knobs
     "tspgpu_tuning_set", "tspgpu_tuning_clear",
 )
@@ -90,6 +92,16 @@ class RefineStats(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int), ("windows", ctypes.c_int64), ("replaced", ctypes.c_int64),
                 ("skipped", ctypes.c_int64), ("gain", ctypes.c_double), ("build_ms", ctypes.c_double),
                 ("k1_ms", ctypes.c_double), ("fold_apply_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TwoOptStats(ctypes.Structure):
+    """tspgpu_two_opt_stats: what a 2-opt call did, and its phase times."""
+    _fields_ = [("passes", ctypes.c_int), ("candidates", ctypes.c_int64), ("moves", ctypes.c_int64),
+                ("gain", ctypes.c_double), ("grid_ms", ctypes.c_double), ("search_ms", ctypes.c_double),
+                ("select_ms", ctypes.c_double), ("apply_ms", ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -245,6 +257,9 @@ def lib():
         L.tspgpu_refine_path.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cp, rsp]
         L.tspgpu_refine_path_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, rsp, vp]
         L.tspgpu_path_length.argtypes = [cp, ctypes.c_int, dp]
+        tsp = ctypes.POINTER(TwoOptStats)
+        L.tspgpu_two_opt_path.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cp, tsp]
+        L.tspgpu_two_opt_path_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, tsp, vp]
         _lib = L
     return _lib
 
@@ -806,19 +821,56 @@ class Context:
                                                     stream_ptr or None), "tspgpu_refine_path_device")
         return st.as_dict()
 
-    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0):
+    def two_opt_path(self, path, ring: int = 2, max_passes: int = 1000):
+        """tspgpu_two_opt_path: a path (list of (id, x, y), closing city included
+        or not) -> (path, stats dict).  Passes of 2-opt moves between spatial
+        neighbours (cells within `ring` of each other on a grid of about L / 2
+        cells): every position's best move is found on the device, the host
+        accepts a disjoint set greedily by gain, the device reverses.  Ends on
+        a pass that finds nothing or after max_passes.  Both end cities stay."""
+        arr, L, _ = cities_array([path])
+        out = (City * max(1, L))()
+        st = TwoOptStats()
+        self._check(lib().tspgpu_two_opt_path(self.handle, arr, L, ring, max_passes, out, ctypes.byref(st)),
+                    "tspgpu_two_opt_path")
+        return [(out[i].id, out[i].x, out[i].y) for i in range(L)], st.as_dict()
+
+    def two_opt_path_device(self, d_path_ptr: int, L: int, ring: int = 2, max_passes: int = 1000,
+                            stream_ptr: int = 0):
+        """tspgpu_two_opt_path_device: L City structs on the device, improved in
+        place; synchronous -> stats dict."""
+        st = TwoOptStats()
+        self._check(lib().tspgpu_two_opt_path_device(self.handle, d_path_ptr, L, ring, max_passes, ctypes.byref(st),
+                                                     stream_ptr or None), "tspgpu_two_opt_path_device")
+        return st.as_dict()
+
+    def _improved(self, result, two_opt: int, refine: int):
+        """(final, log, tour) -> the same with the tour improved and the stats
+        of the stages that ran behind it, 2-opt's first."""
+        final, log, path = result
+        stats = ()
+        if two_opt:
+            path, st = self.two_opt_path(path, 2, two_opt)
+            stats += (st,)
+        if refine:
+            path, st = self.refine_path(path, refine)
+            stats += (st,)
+        return (final, log, path) + stats
+
+    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0, two_opt: int = 0):
         """tspgpu_pipeline_cities: blocks (lists of (id, x, y), or a (ctypes City
         array, n, B) triple) -> (final cost, log text, merged tour as a list of
         (id, x, y)): block search and merges on the device, only the costs
         visit the host in between.  path_cap None: room for (2 + log2 nprocs)
         times the cities, so one run gives the tour; only if that is ever
         short does the whole pipeline run a second time with the reported
-        length.  refine = m > 0: refine_path(tour, m) on the merged tour ->
-        (final cost, log text, refined tour, stats dict); the cost and the log
-        stay the reference's."""
-        if refine:
-            final, log, path = self.pipeline_cities(blocks, nprocs, path_cap)
-            return (final, log) + self.refine_path(path, refine)
+        length.  two_opt = passes > 0: two_opt_path(tour, 2, passes) on the
+        merged tour; refine = m > 0: refine_path(tour, m) behind it -> (final
+        cost, log text, improved tour, the 2-opt stats dict if it ran, the
+        refine stats dict if it ran); the cost and the log stay the
+        reference's."""
+        if refine or two_opt:
+            return self._improved(self.pipeline_cities(blocks, nprocs, path_cap), two_opt, refine)
         arr, n, B = blocks if isinstance(blocks, tuple) else cities_array(blocks)
 
         def call(out, cap):
@@ -915,14 +967,14 @@ class Context:
         return self._path_result("tspgpu_reduce_ragged", call, path_cap,
                                  self._tour_capacity(1, int(lens.sum()), nprocs))
 
-    def pipeline_cities_ragged(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0):
+    def pipeline_cities_ragged(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0,
+                               two_opt: int = 0):
         """tspgpu_pipeline_cities_ragged: blocks of different sizes (lists of
         (id, x, y), or a (ctypes City array, n) pair) -> (final cost, log
-        text, merged tour as a list of (id, x, y)); path_cap and refine as for
-        pipeline_cities."""
-        if refine:
-            final, log, path = self.pipeline_cities_ragged(blocks, nprocs, path_cap)
-            return (final, log) + self.refine_path(path, refine)
+        text, merged tour as a list of (id, x, y)); path_cap, refine and
+        two_opt as for pipeline_cities."""
+        if refine or two_opt:
+            return self._improved(self.pipeline_cities_ragged(blocks, nprocs, path_cap), two_opt, refine)
         arr, n = blocks if isinstance(blocks, tuple) else cities_array_ragged(blocks)
         n = self._ns(n)
         total = int(sum(tour_length(int(k)) for k in n))
