@@ -11,6 +11,14 @@ the contract word for word in Python floats and math.sqrt, quadratic and
 without any neighbour list: a candidate is tested by the definition of N.
 The model tests hold the two against each other.
 
+two_opt() lists the neighbours the way the contract describes them
+(grid_neighbour_pairs(): cities sorted by cell, an exclusive prefix over the
+cell counts, one contiguous run per row), in time near-linear in the number of
+pairs; neighbour_pairs() is the L x L definition it is checked against.  Two
+hooks of two_opt() (axis_cells, pair_filter) exist for the model tests alone:
+they build named WRONG implementations, to show that an input can tell them
+from the right one.
+
 Also the named inputs both sides share; every model result is computed once
 per process (solved())."""
 from __future__ import annotations
@@ -53,12 +61,14 @@ def _axis_cells(v, g: int):
     return np.minimum(g - 1, (((v - lo) / ext) * float(g)).astype(np.int64))
 
 
-def cells(path):
-    """-> (g, cx, cy): the cell of every city (index in the input)."""
+def cells(path, axis_cells=None):
+    """-> (g, cx, cy): the cell of every city (index in the input).
+    axis_cells(v, g) replaces the contract's per-axis formula (mutants only)."""
+    axis_cells = axis_cells or _axis_cells
     g = grid_size(len(path))
     x = np.array([c[1] for c in path], dtype=np.float64)
     y = np.array([c[2] for c in path], dtype=np.float64)
-    return g, _axis_cells(x, g), _axis_cells(y, g)
+    return g, axis_cells(x, g), axis_cells(y, g)
 
 
 def neighbour_pairs(cx, cy, ring: int, rng=None):
@@ -73,15 +83,44 @@ def neighbour_pairs(cx, cy, ring: int, rng=None):
     return u, v
 
 
+def grid_neighbour_pairs(cx, cy, g: int, ring: int, rng=None):
+    """The same set of ordered pairs as neighbour_pairs(), read off the grid
+    as the contract describes it: the cities sorted by cell, start[] the
+    exclusive prefix over the cell counts, and for each of the 2 ring + 1 rows
+    around u the run start[row g + x0] .. start[row g + x1 + 1], x0 and x1
+    clamped at the grid's edge, rows outside the grid left out."""
+    cx = np.asarray(cx, dtype=np.int64)
+    cy = np.asarray(cy, dtype=np.int64)
+    cell = cy * g + cx
+    by_cell = np.argsort(cell, kind="stable")  # slot -> city
+    start = np.concatenate((np.zeros(1, dtype=np.int64), np.cumsum(np.bincount(cell, minlength=g * g))))
+    x0, x1 = np.maximum(cx - ring, 0), np.minimum(cx + ring, g - 1)
+    us, vs = [], []
+    for dy in range(-ring, ring + 1):
+        row = cy + dy
+        city = np.nonzero((row >= 0) & (row < g))[0]
+        s = start[row[city] * g + x0[city]]
+        n = start[row[city] * g + x1[city] + 1] - s
+        first = np.cumsum(n) - n  # where each city's run begins in this row's list
+        us.append(np.repeat(city, n))
+        vs.append(by_cell[np.repeat(s - first, n) + np.arange(int(n.sum()), dtype=np.int64)])
+    u, v = np.concatenate(us), np.concatenate(vs)
+    if rng is not None:
+        k = rng.permutation(len(u))
+        u, v = u[k], v[k]
+    return u, v
+
+
 def _dist(x, y, a, b):
     dx = x[a] - x[b]
     dy = y[a] - y[b]
     return np.sqrt(dx * dx + dy * dy)
 
 
-def best_moves(order, x, y, u, v):
-    """The best move of every position under `order` (city per position):
-    -> (gain, i, j) arrays, one entry per position that has one."""
+def improving_moves(order, x, y, u, v):
+    """Every move with gain > 0 that the pairs reach under `order` (city per
+    position): -> (gain, i, j) arrays; a j that both forms reach is listed
+    twice."""
     L = len(order)
     pos = np.empty(L, dtype=np.int64)
     pos[order] = np.arange(L)
@@ -93,7 +132,13 @@ def best_moves(order, x, y, u, v):
     a, b, c, e = order[i], order[i + 1], order[j], order[j + 1]
     gain = (_dist(x, y, a, b) + _dist(x, y, c, e)) - (_dist(x, y, a, c) + _dist(x, y, b, e))
     ok = gain > 0.0
-    gain, i, j = gain[ok], i[ok], j[ok]
+    return gain[ok], i[ok], j[ok]
+
+
+def best_moves(order, x, y, u, v):
+    """The best move of every position under `order`: -> (gain, i, j) arrays,
+    one entry per position that has one."""
+    gain, i, j = improving_moves(order, x, y, u, v)
     k = np.lexsort((j, -gain, i))  # by i, then the largest gain, then the smallest j
     gain, i, j = gain[k], i[k], j[k]
     first = np.ones(len(i), dtype=bool)
@@ -114,9 +159,12 @@ def select(gain, i, j, L: int):
     return out
 
 
-def two_opt(path, ring: int = 2, max_passes: int = 1000, rng=None, trace=None):
+def two_opt(path, ring: int = 2, max_passes: int = 1000, rng=None, trace=None, axis_cells=None, pair_filter=None):
     """-> (path, stats), or (None, code) for a refused path.  trace: a list
-    that receives each pass's accepted (gain, i, j) list."""
+    that receives each pass's accepted (gain, i, j) list.  The two hooks make
+    wrong implementations for the model tests: axis_cells(v, g) replaces the
+    per-axis cell formula, pair_filter(u, v, cell) -> a mask of the pairs
+    that stay (cell: every city's cell index)."""
     assert 1 <= ring <= 4 and max_passes >= 1 and len(path) >= 1
     code = validate(path)
     if code:
@@ -126,8 +174,11 @@ def two_opt(path, ring: int = 2, max_passes: int = 1000, rng=None, trace=None):
     stats = {"passes": 0, "candidates": 0, "moves": 0, "gain": 0.0}
     if L < 4:
         return path, stats
-    _, cx, cy = cells(path)
-    u, v = neighbour_pairs(cx, cy, ring, rng)
+    g, cx, cy = cells(path, axis_cells)
+    u, v = grid_neighbour_pairs(cx, cy, g, ring, rng)
+    if pair_filter is not None:
+        keep = pair_filter(u, v, cy * g + cx)
+        u, v = u[keep], v[keep]
     x = np.array([c[1] for c in path], dtype=np.float64)
     y = np.array([c[2] for c in path], dtype=np.float64)
     order = np.arange(L)
@@ -264,6 +315,60 @@ def closed_tour(L: int = 250, seed: int = 21):
     return path + [path[0]]
 
 
+def sweep(L: int, seed: int, span: float = 1000.0, reversals: int = 40):
+    """Uniform cities on [0, span]^2, two of them pinned on the corners, in a
+    boustrophedon sweep by grid row (x ascending on even rows, descending on
+    odd ones), then `reversals` random sub-ranges of 3 to 49 positions
+    reversed: a path that is nearly good at any length, so its passes are few
+    and local, with work in every cell of the grid."""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(0.0, span, size=(L, 2))
+    xy[0], xy[1] = (0.0, 0.0), (span, span)
+    g = grid_size(L)
+    row = np.minimum(g - 1, (xy[:, 1] / span * g).astype(np.int64))
+    order = np.lexsort((np.where(row % 2 == 0, xy[:, 0], -xy[:, 0]), row))
+    for _ in range(reversals):
+        n = int(rng.integers(3, 50))
+        s = int(rng.integers(0, L - n + 1))
+        order[s : s + n] = order[s : s + n][::-1].copy()
+    return [(int(k), float(xy[k, 0]), float(xy[k, 1])) for k in order]
+
+
+CELL_EDGE_G, CELL_EDGE_EXT = 11, 7.0
+
+
+def cell_edges(L: int = 242, seed: int = 0):
+    """L = 242 (g = 11, no power of two) uniform cities on [0, 7]^2 in random
+    order, both extents exactly 7; every third city has each coordinate
+    snapped to one of the three doubles around 7 k / 11 (k random in 1..10):
+    the cell border itself and its two neighbours, where the rounding of the
+    quotient and of the product decides the cell."""
+    assert grid_size(L) == CELL_EDGE_G
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(0.0, CELL_EDGE_EXT, size=(L, 2))
+    xy[0], xy[1] = (0.0, 0.0), (CELL_EDGE_EXT, CELL_EDGE_EXT)
+    for c in range(2, L, 3):
+        for axis in (0, 1):
+            edge = CELL_EDGE_EXT * float(rng.integers(1, CELL_EDGE_G)) / float(CELL_EDGE_G)
+            xy[c, axis] = (np.nextafter(edge, -np.inf), edge, np.nextafter(edge, np.inf))[int(rng.integers(0, 3))]
+    return [(500 + k, float(xy[k, 0]), float(xy[k, 1])) for k in range(L)]
+
+
+def scaled(path, exponent: int):
+    """Both coordinates times 2^exponent (exact while nothing under- or overflows)."""
+    return [(c[0], math.ldexp(c[1], exponent), math.ldexp(c[2], exponent)) for c in path]
+
+
+def minus_zero_min():
+    """bow-tie shifted so that both minima are zero, written as -0.0 on one
+    city and as +0.0 on another."""
+    path = [(cid, x + 1.0, y) for cid, x, y in bow_tie()]
+    assert path[0][1] == 0.0 and path[5][1] == 0.0 and path[1][2] == 0.0 and path[3][2] == 0.0
+    path[0] = (path[0][0], -0.0, 0.0)
+    path[1] = (path[1][0], path[1][1], -0.0)
+    return path
+
+
 # name -> (builder, ring, max_passes)
 IDLE_INPUTS = {
     "L1": (functools.partial(R.scrambled, 1, 1), 2, 1000),
@@ -290,7 +395,26 @@ CUT_INPUTS = {
     "scrambled-400-cut1": (functools.partial(R.scrambled, 400, 7), 2, 1),
     "scrambled-400-cut3": (functools.partial(R.scrambled, 400, 7), 2, 3),
 }
-INPUTS = dict(IDLE_INPUTS, **MOVING_INPUTS, **CUT_INPUTS)
+# Past one workgroup of the grid's scan (1024 cells): the smallest lengths with
+# g = 33 (two scan workgroups, the last one ragged), g = 66 (five) and g = 513
+# (258 first-level workgroups: two items per lane in the second level).
+SWEEP_INPUTS = {
+    "sweep-2178": (functools.partial(sweep, 2178, 31), 2, 1000),
+    "sweep-8712-ring3": (functools.partial(sweep, 8712, 32), 3, 1000),
+    "sweep-526338-ring1-cut3": (functools.partial(sweep, 526338, 33), 1, 3),
+}
+SCALED_BASE = "scrambled-400"
+SCALED_INPUTS = {
+    f"{SCALED_BASE}-x2^{e}": (functools.partial(scaled, R.scrambled(400, 7), e), 2, 1000) for e in (500, -500, -520)
+}
+# (exponent, code): the two neighbours of the -ERANGE limit, SCALED_BASE times 2^exponent
+RANGE_EDGE = ((501, 0), (502, -errno.ERANGE))
+EDGE_INPUTS = {
+    "cell-edges-242": (cell_edges, 1, 1000),
+    "minus-zero-min": (minus_zero_min, 2, 1000),
+}
+SCALE_INPUTS = dict(SWEEP_INPUTS, **SCALED_INPUTS, **EDGE_INPUTS)  # what tests/test_two_opt_scale_gpu.py runs
+INPUTS = dict(IDLE_INPUTS, **MOVING_INPUTS, **CUT_INPUTS, **SCALE_INPUTS)
 
 
 @functools.lru_cache(maxsize=None)
