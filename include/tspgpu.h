@@ -801,6 +801,77 @@ int tspgpu_two_opt_path(tspgpu_ctx *ctx, const tspgpu_city *path, int L, int rin
                         tspgpu_city *path_out, tspgpu_two_opt_stats *stats);
 
 /* ---------------------------------------------------------------------------
+ * Or-opt with a neighbour grid (an extension: the reference
+ * has no counterpart).  Segment insertion, the move that neither 2-opt nor a
+ * window reaches: 1 to 3 consecutive cities leave the tour and go back in,
+ * either way round, next to a city that is close in the plane and arbitrarily
+ * far in tour order.  The whole contract is below and in "2-opt with a
+ * neighbour grid" above; tests/or_opt_model.py is the same in Python, and the
+ * device matches it bit for bit.
+ *
+ * Unchanged from 2-opt: a path of 1 <= L <= 2^30 cities, "city" = index in
+ * the input; the distance d (f64, no contraction, correctly rounded sqrt);
+ * the validation, its codes and their order, with nothing written on an
+ * error; the grid, g, the cell formula and N(c) with ring in 1..4; positions
+ * 0 and L-1 never move.  New: max_seg outside 1..3 is -EINVAL with the other
+ * arguments.  L < 4 (after the checks): 0 with passes = 0, the path untouched.
+ *
+ * Moves.  With p the current order, move (a, k, t, rev) takes the segment of
+ * positions a..h, h = a+k-1, 1 <= k <= max_seg, 1 <= a, h <= L-2, and puts it
+ * into edge t (between positions t and t+1), 0 <= t <= L-2, t outside
+ * [a-1, h].  With first = p[a], last = p[h], P = p[a-1], N = p[h+1], c = p[t],
+ * e = p[t+1]: rev = 0 puts the segment in as it lies, x = first follows c and
+ * y = last precedes e; rev = 1 puts it in reversed, x = last and y = first;
+ * k = 1 has rev = 0 only.
+ *   gain = ((d(P,first) + d(last,N)) + d(c,e)) - ((d(P,N) + d(c,x)) + d(y,e))
+ * in exactly that order of operations: a function of the move, not of how it
+ * was found.  Applying it: if t > h, positions a..t become p[h+1..t] followed
+ * by the (reversed) segment, and its edge range is [lo, hi] = [a-1, t]; if
+ * t < a-1, positions t+1..h become the (reversed) segment followed by
+ * p[t+1..a-1], and [lo, hi] = [t, h].  Either way a rotation of positions
+ * lo+1..hi.
+ *
+ * Candidates of position s, 1 <= s <= L-2, f = p[s]: the segments with f at
+ * one end, [s, s+k-1] and [s-k+1, s] for k <= max_seg, those that leave
+ * 1..L-2 dropped, k = 1 counted once; for each of them and every v in N(f),
+ * v != f, at position q, the two insertions that make f adjacent to v:
+ * t = q (c = v, f is x) and t = q-1 (e = v, f is y), rev following from the
+ * end f is and the side it lands on; illegal t dropped.  The best move of s
+ * is the largest gain > 0, on equal gains the lexicographically smallest
+ * (a, k, t, rev); a move reached twice is one move; it may not exist.
+ * Nothing prunes the candidates.  A segment whose other end is the one near v
+ * is found by that end's position, so the neighbourhood is complete, and one
+ * move may be reported by two positions.
+ *
+ * A pass.  (1) The best move of every s, all under the order at the start of
+ * the pass.  (2) Sort the existing ones by (gain descending, s ascending).
+ * (3) In that order accept a move iff its [lo, hi] is disjoint from that of
+ * every move accepted before; hi + 1 = lo' is compatible.  (4) gain = gain +
+ * g_k for every accepted move in acceptance order, a left fold.  (5) Apply
+ * all accepted moves.  A pass that accepts nothing is counted and ends the
+ * call, as does reaching max_passes.  Every choice is a total order, so the
+ * result is a function of the input alone: a permutation of it with both
+ * ends in place.
+ * ------------------------------------------------------------------------- */
+typedef struct
+{
+    int passes;         /* passes run (the last, empty one included) */
+    int64_t candidates; /* best moves sent to the selection, summed over the passes */
+    int64_t moves;      /* moves accepted and applied */
+    double gain;        /* the left fold of the accepted gains */
+    /* as in tspgpu_two_opt_stats (apply_ms: the stage and commit kernels) */
+    double grid_ms, search_ms, select_ms, apply_ms;
+} tspgpu_or_opt_stats;
+/* In place on the device; synchronous (the host selects after every pass).
+ * stats may be NULL. */
+int tspgpu_or_opt_path_device(tspgpu_ctx *ctx, tspgpu_city *d_path, int L, int ring, int max_seg, int max_passes,
+                              tspgpu_or_opt_stats *stats, void *hip_stream);
+/* Host form: path up, the device form on the context's stream, path_out (L
+ * cities; may be path itself) down. */
+int tspgpu_or_opt_path(tspgpu_ctx *ctx, const tspgpu_city *path, int L, int ring, int max_seg, int max_passes,
+                       tspgpu_city *path_out, tspgpu_or_opt_stats *stats);
+
+/* ---------------------------------------------------------------------------
  * Tuning and test knobs.  The defaults are the measured best; a knob changes
  * how the kernels run (K1 variant / configuration, buffer sizes, a bound
  * switched off for an A/B run, a fallback forced by a test), never the

@@ -61,6 +61,21 @@ int cities_args(const tspgpu_ctx *c, const void *cities, int n, const int32_t *n
 int cities_build_locked(tspgpu_ctx *c, const tspgpu_city *d_cities, int n, int nblocks, double *d_dist,
                         hipStream_t stream, const int32_t *ns = nullptr, int skip_above = TSPGPU_MAX_CITIES);
 
+// ---- two_opt_abi.cpp ----
+// What the 2-opt and Or-opt stages share (or_opt_abi.cpp): d_to_words holds
+// the bounds and, behind them, a pass's candidate counter.
+constexpr size_t kToCountAt = 64;
+constexpr size_t kToWordsBytes = 128;
+// The start of either stage on `stream` (c->mu held): the d_to_* buffers and
+// the events reserved for L cities, the workspace waited for, d_path ->
+// px, py, ord = pos = identity, the coordinates validated (-EINVAL, -ERANGE)
+// and, from L = 4 up, the grid of *g by *g cells built and d_path copied to
+// d_to_in; ev_to[0] and ev_to[1] stand around it all.  The bounds have been
+// waited for, the grid kernels are left running.
+int two_opt_state_locked(tspgpu_ctx *c, const tspgpu_city *d_path, int L, hipStream_t stream, int *g);
+// *sum += the milliseconds between two recorded events that have passed
+int two_opt_add_ms(double *sum, hipEvent_t from, hipEvent_t to);
+
 // One buffer of a host form: reserved, then copied to or from `host`
 struct HostCopy {
     DevBuf<char> *buf;

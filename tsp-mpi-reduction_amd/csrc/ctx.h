@@ -117,6 +117,17 @@ struct tspgpu_ctx {
     tspgpu::Pinned<char> h_to_cand, h_to_words;
     tspgpu::Pinned<int32_t> h_to_acc;
     tspgpu::Event ev_to[6];
+    // Or-opt with a neighbour grid (or_opt_abi.cpp) runs on
+    // the 2-opt stage's path, state, grid, words and events, and adds a
+    // pass's candidates and accepted moves (lo, hi, how, length prefix) with
+    // their pinned twins and the scratch a rotation is staged in (ord, px,
+    // py of the rotated positions).  Per context and under the K1 ordering
+    // rule.
+    tspgpu::DevBuf<char> d_oo_cand;
+    tspgpu::DevBuf<int32_t> d_oo_acc, d_oo_ord;
+    tspgpu::DevBuf<double> d_oo_px, d_oo_py;
+    tspgpu::Pinned<char> h_oo_cand;
+    tspgpu::Pinned<int32_t> h_oo_acc;
     // the last tspgpu_reduce_device's gather + summary + uniqueness kernels,
     // from HIP events (tspgpu_reduce_device_last_ms)
     double k3_gather_ms = 0.0;

@@ -21,11 +21,9 @@
 
 using namespace tspgpu;
 
-namespace {
+static_assert(sizeof(TwoOptBounds) <= kToCountAt, "the counter stands behind the bounds");
 
-constexpr size_t kCountAt = 64;  // the candidate counter's place in d_to_words, behind the bounds
-constexpr size_t kWordsBytes = 128;
-static_assert(sizeof(TwoOptBounds) <= kCountAt, "the counter stands behind the bounds");
+namespace {
 
 // the call-level checks of both forms
 int two_opt_args(const tspgpu_ctx *c, const void *path, int L, int ring, int max_passes)
@@ -52,7 +50,7 @@ int two_opt_reserve(tspgpu_ctx *c, int L, int cells)
     int rc = 0;
     if ((rc = dev_reserve(c->d_to_in, n * sizeof(tspgpu_city)))) return rc;
     if ((rc = dev_reserve(c->d_to_cand, n * sizeof(TwoOptCand)))) return rc;
-    if ((rc = dev_reserve(c->d_to_words, kWordsBytes))) return rc;
+    if ((rc = dev_reserve(c->d_to_words, kToWordsBytes))) return rc;
     if ((rc = dev_reserve(c->d_to_ord, n * i32))) return rc;
     if ((rc = dev_reserve(c->d_to_pos, n * i32))) return rc;
     if ((rc = dev_reserve(c->d_to_cell, n * i32))) return rc;
@@ -66,12 +64,14 @@ int two_opt_reserve(tspgpu_ctx *c, int L, int cells)
     if ((rc = dev_reserve(c->d_to_cx, n * f64))) return rc;
     if ((rc = dev_reserve(c->d_to_cy, n * f64))) return rc;
     if ((rc = pinned_reserve(c->h_to_cand, n * sizeof(TwoOptCand)))) return rc;
-    if ((rc = pinned_reserve(c->h_to_words, kWordsBytes))) return rc;
+    if ((rc = pinned_reserve(c->h_to_words, kToWordsBytes))) return rc;
     if ((rc = pinned_reserve(c->h_to_acc, acc))) return rc;
     return two_opt_events(c);
 }
 
-int add_ms(double *sum, hipEvent_t from, hipEvent_t to)
+}  // namespace
+
+int tspgpu::two_opt_add_ms(double *sum, hipEvent_t from, hipEvent_t to)
 {
     float ms = 0.0f;
     const hipError_t e = hipEventElapsedTime(&ms, from, to);
@@ -80,23 +80,16 @@ int add_ms(double *sum, hipEvent_t from, hipEvent_t to)
     return 0;
 }
 
-// The whole call on `stream` (c->mu held): synchronous.  d_path is written by
-// the emit kernel alone, after every check has passed.
-int two_opt_locked(tspgpu_ctx *c, tspgpu_city *d_path, int L, int ring, int max_passes, tspgpu_two_opt_stats *st,
-                   hipStream_t stream)
+int tspgpu::two_opt_state_locked(tspgpu_ctx *c, const tspgpu_city *d_path, int L, hipStream_t stream, int *g_out)
 {
     if (hipSetDevice(c->device) != hipSuccess) return -ENODEV;
-    const int g = two_opt_grid(L), cells = g * g;
+    const int g = *g_out = two_opt_grid(L), cells = g * g;
     int rc = two_opt_reserve(c, L, cells);
     if (rc) return rc;
     // every buffer below is the context's: under the workspace ordering rule
     if ((rc = workspace_wait(c, stream))) return rc;
     TwoOptBounds *d_bounds = reinterpret_cast<TwoOptBounds *>(c->d_to_words.p);
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(c->d_to_words.p + kCountAt);
     TwoOptBounds *h_bounds = reinterpret_cast<TwoOptBounds *>(c->h_to_words.p);
-    uint32_t *h_count = reinterpret_cast<uint32_t *>(c->h_to_words.p + kCountAt);
-    TwoOptCand *d_cand = reinterpret_cast<TwoOptCand *>(c->d_to_cand.p);
-    TwoOptCand *h_cand = reinterpret_cast<TwoOptCand *>(c->h_to_cand.p);
 
     // bounds + validation; the state starts as the identity order
     *h_bounds = two_opt_bounds_init();
@@ -126,7 +119,24 @@ int two_opt_locked(tspgpu_ctx *c, tspgpu_city *d_path, int L, int ring, int max_
     if (e == hipSuccess)
         e = hipMemcpyAsync(c->d_to_in, d_path, (size_t)L * sizeof(tspgpu_city), hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipEventRecord(c->ev_to[1], stream);
-    if (e != hipSuccess) return hip_err(e);
+    return hip_err(e);
+}
+
+namespace {
+
+// The whole call on `stream` (c->mu held): synchronous.  d_path is written by
+// the emit kernel alone, after every check has passed.
+int two_opt_locked(tspgpu_ctx *c, tspgpu_city *d_path, int L, int ring, int max_passes, tspgpu_two_opt_stats *st,
+                   hipStream_t stream)
+{
+    int g = 0;
+    int rc = two_opt_state_locked(c, d_path, L, stream, &g);
+    if (rc || L < 4) return rc;  // L < 4: no legal move
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(c->d_to_words.p + kToCountAt);
+    uint32_t *h_count = reinterpret_cast<uint32_t *>(c->h_to_words.p + kToCountAt);
+    TwoOptCand *d_cand = reinterpret_cast<TwoOptCand *>(c->d_to_cand.p);
+    TwoOptCand *h_cand = reinterpret_cast<TwoOptCand *>(c->h_to_cand.p);
+    hipError_t e = hipSuccess;
 
     int32_t *h_i = c->h_to_acc.p, *h_j = h_i + (L / 3 + 1), *h_prefix = h_j + (L / 3 + 1);
     int32_t *d_i = c->d_to_acc.p, *d_j = d_i + (L / 3 + 1), *d_prefix = d_j + (L / 3 + 1);
@@ -141,9 +151,9 @@ int two_opt_locked(tspgpu_ctx *c, tspgpu_city *d_path, int L, int ring, int max_
         if (e == hipSuccess) e = hipMemcpyAsync(h_count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         if (e != hipSuccess) return hip_err(e);
-        if (!grid_timed && (rc = add_ms(&st->grid_ms, c->ev_to[0], c->ev_to[1]))) return rc;
+        if (!grid_timed && (rc = two_opt_add_ms(&st->grid_ms, c->ev_to[0], c->ev_to[1]))) return rc;
         grid_timed = true;
-        if ((rc = add_ms(&st->search_ms, c->ev_to[2], c->ev_to[3]))) return rc;
+        if ((rc = two_opt_add_ms(&st->search_ms, c->ev_to[2], c->ev_to[3]))) return rc;
         const int64_t n = *h_count;
         if (n > (int64_t)L - 3) return -EIO;  // more candidates than positions: the list is not ours
         if (n > 0) {
@@ -171,7 +181,7 @@ int two_opt_locked(tspgpu_ctx *c, tspgpu_city *d_path, int L, int ring, int max_
         // (the next selection writes the pinned lists again: the uploads must have read them)
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         if (e != hipSuccess) return hip_err(e);
-        if ((rc = add_ms(&st->apply_ms, c->ev_to[4], c->ev_to[5]))) return rc;
+        if ((rc = two_opt_add_ms(&st->apply_ms, c->ev_to[4], c->ev_to[5]))) return rc;
         if (st->passes == max_passes) break;
     }
     if (st->moves > 0) {

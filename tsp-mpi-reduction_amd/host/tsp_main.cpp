@@ -46,6 +46,11 @@
 // if both are set and like it after the clock, with one stderr line of its
 // own: length before and after, passes, moves, gain.  If it fails the tour
 // goes on as merged.
+// TSP_OR_OPT=passes (with TSP_TOUR_OUT) runs Or-opt between spatial neighbours
+// (tspgpu_or_opt_path: segments of up to TSP_OR_OPT_SEG cities, default 3,
+// cells within TSP_OR_OPT_RING of each other, default 2) after TSP_TWO_OPT
+// and before TSP_REFINE, with a stderr line in the 2-opt line's style.  If it
+// fails the tour goes on as it stood.
 //
 // Deviations (documented in DESIGN.md), all where the reference is undefined:
 // n < 2, numBlocks < 1 or numBlocks < P exit 2 with a message on stderr
@@ -508,8 +513,10 @@ int main(int argc, char **argv)
     const int two_opt_passes = env_int("TSP_TWO_OPT", 0);
     const bool improvable = tour_file && merged_len >= 0 && kept;
     const bool refine = refine_m > 0 && improvable;
+    const int or_opt_passes = env_int("TSP_OR_OPT", 0);
     const bool two_opt = two_opt_passes > 0 && improvable;
-    if (refine || two_opt) {
+    const bool or_opt = or_opt_passes > 0 && improvable;
+    if (refine || two_opt || or_opt) {
         // (improved and written below, once the clock has stopped)
     } else if (tour_file && merged_len >= 0) {
         const int wrc = write_tour(tour_file, merged.data(), merged_len);
@@ -539,6 +546,27 @@ int main(int argc, char **argv)
         else
             std::fprintf(stderr, "tsp two-opt: ring %d | tour length %f -> %f | %d passes, %lld moves, gain %f\n", ring,
                          before, after, ts.passes, (long long)ts.moves, ts.gain);
+        if (!refine && !or_opt) {
+            const int wrc = write_tour(tour_file, merged.data(), merged_len);
+            if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));
+        }
+    }
+    if (or_opt) {
+        double before = 0.0, after = 0.0;
+        const int ring = env_int("TSP_OR_OPT_RING", 2), seg = env_int("TSP_OR_OPT_SEG", 3);
+        tspgpu_or_opt_stats os;
+        std::memset(&os, 0, sizeof os);
+        (void)tspgpu_path_length(merged.data(), merged_len, &before);
+        const int orc =
+            tspgpu_or_opt_path(kept, merged.data(), merged_len, ring, seg, or_opt_passes, merged.data(), &os);
+        (void)tspgpu_path_length(merged.data(), merged_len, &after);
+        if (orc)
+            std::fprintf(stderr, "tsp: TSP_OR_OPT=%d failed, the tour is written as it stood: %s (%d)\n", or_opt_passes,
+                         tspgpu_strerror(orc), orc);
+        else
+            std::fprintf(stderr,
+                         "tsp or-opt: ring %d, segments to %d | tour length %f -> %f | %d passes, %lld moves, gain %f\n",
+                         ring, seg, before, after, os.passes, (long long)os.moves, os.gain);
         if (!refine) {
             const int wrc = write_tour(tour_file, merged.data(), merged_len);
             if (wrc) std::fprintf(stderr, "tsp: TSP_TOUR_OUT %s: %s\n", tour_file, std::strerror(-wrc));

@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "tspgpu_refine_path", "tspgpu_refine_path_device", "tspgpu_path_length",
     # 2-opt with a neighbour grid on a path, the stage in front of the window refinement
     "tspgpu_two_opt_path", "tspgpu_two_opt_path_device",
+    # Or-opt (segment insertion) on the same grid, between 2-opt and the window refinement
+    "tspgpu_or_opt_path", "tspgpu_or_opt_path_device",
     # tuning / test knobs
     "tspgpu_tuning_set", "tspgpu_tuning_clear",
 )
@@ -102,6 +104,14 @@ class TwoOptStats(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_int), ("candidates", ctypes.c_int64), ("moves", ctypes.c_int64),
                 ("gain", ctypes.c_double), ("grid_ms", ctypes.c_double), ("search_ms", ctypes.c_double),
                 ("select_ms", ctypes.c_double), ("apply_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OrOptStats(ctypes.Structure):
+    """tspgpu_or_opt_stats: what an Or-opt call did, and its phase times."""
+    _fields_ = list(TwoOptStats._fields_)
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -260,6 +270,9 @@ def lib():
         tsp = ctypes.POINTER(TwoOptStats)
         L.tspgpu_two_opt_path.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, cp, tsp]
         L.tspgpu_two_opt_path_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, tsp, vp]
+        osp = ctypes.POINTER(OrOptStats)
+        L.tspgpu_or_opt_path.argtypes = [vp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, cp, osp]
+        L.tspgpu_or_opt_path_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, osp, vp]
         _lib = L
     return _lib
 
@@ -844,20 +857,49 @@ class Context:
                                                      stream_ptr or None), "tspgpu_two_opt_path_device")
         return st.as_dict()
 
-    def _improved(self, result, two_opt: int, refine: int):
+    def or_opt_path(self, path, ring: int = 2, max_seg: int = 3, max_passes: int = 1000):
+        """tspgpu_or_opt_path: a path (list of (id, x, y), closing city included
+        or not) -> (path, stats dict).  Passes of Or-opt moves between spatial
+        neighbours (the 2-opt stage's grid): segments of up to max_seg cities
+        are taken out and put back, either way round, next to a city within
+        `ring` cells; every position's best move is found on the device, the
+        host accepts a disjoint set greedily by gain, the device rotates.
+        Ends on a pass that finds nothing or after max_passes.  Both end
+        cities stay."""
+        arr, L, _ = cities_array([path])
+        out = (City * max(1, L))()
+        st = OrOptStats()
+        self._check(lib().tspgpu_or_opt_path(self.handle, arr, L, ring, max_seg, max_passes, out, ctypes.byref(st)),
+                    "tspgpu_or_opt_path")
+        return [(out[i].id, out[i].x, out[i].y) for i in range(L)], st.as_dict()
+
+    def or_opt_path_device(self, d_path_ptr: int, L: int, ring: int = 2, max_seg: int = 3, max_passes: int = 1000,
+                           stream_ptr: int = 0):
+        """tspgpu_or_opt_path_device: L City structs on the device, improved in
+        place; synchronous -> stats dict."""
+        st = OrOptStats()
+        self._check(lib().tspgpu_or_opt_path_device(self.handle, d_path_ptr, L, ring, max_seg, max_passes,
+                                                    ctypes.byref(st), stream_ptr or None), "tspgpu_or_opt_path_device")
+        return st.as_dict()
+
+    def _improved(self, result, two_opt: int, refine: int, or_opt: int = 0):
         """(final, log, tour) -> the same with the tour improved and the stats
-        of the stages that ran behind it, 2-opt's first."""
+        of the stages that ran behind it: 2-opt's, Or-opt's, the refinement's."""
         final, log, path = result
         stats = ()
         if two_opt:
             path, st = self.two_opt_path(path, 2, two_opt)
+            stats += (st,)
+        if or_opt:
+            path, st = self.or_opt_path(path, 2, 3, or_opt)
             stats += (st,)
         if refine:
             path, st = self.refine_path(path, refine)
             stats += (st,)
         return (final, log, path) + stats
 
-    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0, two_opt: int = 0):
+    def pipeline_cities(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0, two_opt: int = 0,
+                        or_opt: int = 0):
         """tspgpu_pipeline_cities: blocks (lists of (id, x, y), or a (ctypes City
         array, n, B) triple) -> (final cost, log text, merged tour as a list of
         (id, x, y)): block search and merges on the device, only the costs
@@ -865,12 +907,12 @@ class Context:
         times the cities, so one run gives the tour; only if that is ever
         short does the whole pipeline run a second time with the reported
         length.  two_opt = passes > 0: two_opt_path(tour, 2, passes) on the
-        merged tour; refine = m > 0: refine_path(tour, m) behind it -> (final
-        cost, log text, improved tour, the 2-opt stats dict if it ran, the
-        refine stats dict if it ran); the cost and the log stay the
-        reference's."""
-        if refine or two_opt:
-            return self._improved(self.pipeline_cities(blocks, nprocs, path_cap), two_opt, refine)
+        merged tour; or_opt = passes > 0: or_opt_path(tour, 2, 3, passes)
+        behind it; refine = m > 0: refine_path(tour, m) behind both -> (final
+        cost, log text, improved tour, then the stats dict of every stage
+        that ran, in that order); the cost and the log stay the reference's."""
+        if refine or two_opt or or_opt:
+            return self._improved(self.pipeline_cities(blocks, nprocs, path_cap), two_opt, refine, or_opt)
         arr, n, B = blocks if isinstance(blocks, tuple) else cities_array(blocks)
 
         def call(out, cap):
@@ -968,13 +1010,13 @@ class Context:
                                  self._tour_capacity(1, int(lens.sum()), nprocs))
 
     def pipeline_cities_ragged(self, blocks, nprocs: int, path_cap: int | None = None, refine: int = 0,
-                               two_opt: int = 0):
+                               two_opt: int = 0, or_opt: int = 0):
         """tspgpu_pipeline_cities_ragged: blocks of different sizes (lists of
         (id, x, y), or a (ctypes City array, n) pair) -> (final cost, log
-        text, merged tour as a list of (id, x, y)); path_cap, refine and
-        two_opt as for pipeline_cities."""
-        if refine or two_opt:
-            return self._improved(self.pipeline_cities_ragged(blocks, nprocs, path_cap), two_opt, refine)
+        text, merged tour as a list of (id, x, y)); path_cap, refine, two_opt
+        and or_opt as for pipeline_cities."""
+        if refine or two_opt or or_opt:
+            return self._improved(self.pipeline_cities_ragged(blocks, nprocs, path_cap), two_opt, refine, or_opt)
         arr, n = blocks if isinstance(blocks, tuple) else cities_array_ragged(blocks)
         n = self._ns(n)
         total = int(sum(tour_length(int(k)) for k in n))
